@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the AWQ int4 quantized-linear hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -23,11 +23,17 @@ region contains exactly K steps of device work and no Python.
 
 Prints ONE JSON line (rank 0).  `value` is whole-job algorithmic GB/s: bytes every rank must move (packed weight +
 activations + outputs = 23,455,232 B per GEMV at the headline shape) divided by the slowest rank's wall time over
-the K timed steps (barrier + synchronize on both sides).  `roofline` prices the dominant kernel (the fused GEMV)
-against 8 TB/s from HIP events around the same K steps (all K steps are one graph replay, kernel boundaries included);
-`cpu_baseline` times the reference's CPU form of the same linear on this host.
+the K timed steps (barrier + synchronize on both sides); `ms_per_step` is that wall time per step.
 
-At N = 1 the same line also carries the rest of BASELINE.json's metric, each measured in this run:
+A plain run does only that: set-up, W warm-up steps, the K timed steps, the JSON line.  `--dump-outputs DIR` also writes what the
+last timed step computed, one `DIR/y<j>_<col|row>.npy` (float32) per linear of the step: the [M, N_out] result a caller of the
+layer receives.  Inputs are seeded, so two runs with the same arguments write comparable files.
+
+`--full` adds everything else the benchmark measures or checks, in runs of its own outside the timed region:
+a parity spot-check of the first linear against the oracle before anything is timed; `roofline`, which prices the dominant
+kernel (the fused GEMV) against 8 TB/s from HIP events around a second pass of the same K steps (all K steps are one graph
+replay, kernel boundaries included); `cpu_baseline`, which times the reference's CPU form of the same linear on this host
+(`--cpu-seconds`); and, at N = 1, the rest of BASELINE.json's metric (`--sections`), each measured in this run:
   `prefill`        awq_gemm at M = 2048 (configs[2]): us, TFLOP/s, roofline against 2.5 PFLOP/s dense fp16;
   `dequantize`     awq_dequantize 4096 x 11008 (configs[0]'s op on the GPU): us, GB/s against 113,602,560 B;
   `awq_gemm_op`    the drop-in `sgl_kernel.awq_gemm` op on the checkpoint tensors (M = 1 and M = 2048);
@@ -80,9 +86,13 @@ def parse_args():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--shapes", choices=["baseline", "70b-tp8"], default="baseline")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a HIP graph")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: oracle spot-check, roofline (HIP-event pass), cpu_baseline and the --sections records")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: budget of the cpu_baseline leg (0 = skip)")
     ap.add_argument("--sections", default="prefill,dequantize,op,decode,large",
-                    help="extra records measured at N = 1 beside the headline (comma list; '' = none)")
+                    help="with --full: extra records measured at N = 1 beside the headline (comma list; '' = none)")
     return ap.parse_args()
 
 
@@ -117,6 +127,23 @@ def cpu_baseline(budget_s: float, M: int):
             "kind": "port", "ms_per_linear": round(per * 1e3, 2),
             "sample": f"{iters} x (eager torch CPU dequantise + matmul) of the same M={M} K={K_DIM} N={N_DIM} g={GROUP} fp16 linear, "
                       f"{el:.1f} s on {torch.get_num_threads()} threads ({os.cpu_count()} logical CPUs)"}
+
+
+DUMP_BYTES_MAX = 32 << 20       # of array data per --dump-outputs directory
+
+
+def dump_outputs(dirname: str, named):
+    """Write each (name, array) as dirname/name.npy in float32; an array over its share of DUMP_BYTES_MAX is cut down to a
+    fixed, seeded sample of its elements (sorted flat indices, the same in every run)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_BYTES_MAX // 4 // max(1, len(named))
+    for name, a in named:
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(20240601).integers(0, a.size, cap))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def pmc_traffic(kernel_substr: str, tag: str = "*m1*"):
@@ -277,7 +304,7 @@ def main():
     xs = make_x(M)
 
     # ---- parity spot-check of set 0's first linear against the oracle (rank 0; the checker, not the measured path)
-    if rank == 0 and not cpu_rehearsal:
+    if args.full and rank == 0 and not cpu_rehearsal:
         from oracle import c_oracle
 
         kind0, K0, N0 = rank_shapes[0]
@@ -291,16 +318,19 @@ def main():
             if not np.all(np.abs(got - exact) <= 0.5 * ulp + 1e-3):
                 raise SystemExit("bench: GPU result does not match the oracle; refusing to time a wrong kernel")
 
-    def step(i, layers=None, inputs=None):
+    def step(i, layers=None, inputs=None, keep=None):
         layers = layers if layers is not None else layer_sets[i % sets]
         inputs = inputs if inputs is not None else xs
         for layer, x in zip(layers, inputs):
-            layer(x)                      # a row-parallel linear includes the all-reduce when tp > 1
+            y = layer(x)                  # a row-parallel linear includes the all-reduce when tp > 1
+            if keep is not None:
+                keep.append(y[0])
 
     # ---- graphs: one holding all K timed steps (a single replay in the timed region), one for the warm-up -------
     use_graph = not args.no_graph and not test_backend and not cpu_rehearsal
     capture_error = None
     graphs = {}
+    graph_outs = {}                    # per graph of n steps: the output tensors of its last step (they live in the graph's pool)
 
     cap_stream = None
 
@@ -321,15 +351,24 @@ def main():
 
     MAX_GRAPH_STEPS = 256
 
+    def capture_steps(n):
+        outs = []
+        graphs[n] = capture(n, lambda i: step(i, keep=outs if i == n - 1 else None))
+        graph_outs[n] = outs
+
     def run_steps(n):
+        """Run n steps; returns the outputs of the last one (one tensor per linear of the step)."""
+        outs = []
         if not use_graph:
             for i in range(n):
-                step(i)
-            return
+                step(i, keep=outs if i == n - 1 else None)
+            return outs
         while n > 0:
             k = n if n in graphs else (MAX_GRAPH_STEPS if n >= MAX_GRAPH_STEPS and MAX_GRAPH_STEPS in graphs else sets if n >= sets and sets in graphs else 1)
             graphs[k].replay()
+            outs = graph_outs[k]
             n -= k
+        return outs
 
     for i in range(int(os.environ.get("BENCH_EAGER_PASSES", "1")) * sets):
         step(i)                        # eager set-up pass over every weight set: workspace allocation, RCCL communicator, page tables
@@ -337,13 +376,14 @@ def main():
     if use_graph:
         try:
             for n in sorted({min(args.steps, MAX_GRAPH_STEPS), min(max(args.warmup, 1), MAX_GRAPH_STEPS), sets, 1}):
-                graphs[n] = capture(n)
+                capture_steps(n)
         except Exception as e:         # e.g. a collective that cannot be captured on this stack
             capture_error = repr(e)
             if rank == 0:
                 print(f"bench: graph capture failed ({e!r}); falling back to eager launches", file=sys.stderr)
             use_graph = False
             graphs.clear()
+            graph_outs.clear()
             sync()
     if world > 1 and not args.no_graph and not test_backend and not cpu_rehearsal:
         # every rank replays or every rank launches eagerly: a rank whose capture failed must not leave the others replaying
@@ -352,17 +392,19 @@ def main():
         if int(ok.item()) == 0 and use_graph:
             use_graph = False
             graphs.clear()
+            graph_outs.clear()
             capture_error = capture_error or "capture failed on another rank"
         sync()
 
 
     def timed_wall(n):
-        """The contract's timed region: barrier + synchronize, n steps, synchronize + barrier; wall seconds."""
+        """The contract's timed region: barrier + synchronize, n steps, synchronize + barrier; wall seconds and the last
+        step's outputs."""
         tp.barrier(); sync()
         t0 = time.perf_counter()
-        run_steps(n)
+        outs = run_steps(n)
         sync(); tp.barrier()
-        return time.perf_counter() - t0
+        return time.perf_counter() - t0, outs
 
     def timed_events(n, runner=None):
         """The same n steps between HIP events on the launch stream (torch's current stream): device time of the kernels
@@ -388,14 +430,18 @@ def main():
             run_steps(max(args.warmup, sets))
             clock_warm += max(args.warmup, sets)
             sync()
-    wall = timed_wall(args.steps)
-    ev = timed_events(args.steps)
+    wall, last_outs = timed_wall(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [(f"y{j}_{kind}", y.detach().float().cpu().numpy())
+                                         for j, ((kind, _, _), y) in enumerate(zip(rank_shapes, last_outs))])
+    del last_outs
+    ev = timed_events(args.steps) if args.full else float("nan")
     if world > 1:
         tmax = torch.tensor([wall, ev if ev == ev else 0.0], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         wall, ev = float(tmax[0]), float(tmax[1])
 
-    sections = set(s for s in args.sections.split(",") if s) if (world == 1 and rank == 0 and not cpu_rehearsal and args.shapes == "baseline"
+    sections = set(s for s in args.sections.split(",") if s) if (args.full and world == 1 and rank == 0 and not cpu_rehearsal and args.shapes == "baseline"
                                                                  and args.scaling == "weak") else set()
 
     def graph_time(fn_pass, launches_per_pass, min_launches, max_seconds=2.0):
@@ -526,7 +572,7 @@ def main():
     # ---- Llama-2-7B-AWQ decode, TP = 1 (BASELINE configs[3]) ----------------------------------------------------
     decode = None
     if "decode" in sections:
-        del layer_sets, graphs
+        del layer_sets, graphs, graph_outs
         torch.cuda.empty_cache()
         import bench_decode
 
@@ -594,7 +640,7 @@ def main():
     for name, rec in (("prefill", prefill), ("dequantize", dequant), ("awq_gemm_op", op_rec), ("decode_7b_tp1", decode)):
         if rec is not None:
             out[name] = rec
-    if world == 1 and args.cpu_seconds > 0 and not cpu_rehearsal:
+    if args.full and world == 1 and args.cpu_seconds > 0 and not cpu_rehearsal:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, M)
     print(json.dumps(out), flush=True)
     if world > 1:
