@@ -55,6 +55,13 @@ int awq_aux_gemv_repacked_fused(const void* x, int64_t ldx, const void* packed, 
                                 int64_t group_size, int dtype, const void* norm_h, const void* norm_delta, const void* norm_w,
                                 void* norm_h_out, float norm_eps, int silu_mul, void* stream);
 
+/* The same with the kernel forced (awq_hip.h: enum awq_repacked_variant).  AWQ_RP_AUTO: exactly awq_aux_gemv_repacked_fused (which takes
+ * the shared-activation kernel on its own for the SiLU-mul epilogue alone at 17 .. 32 rows).  AWQ_RP_SHARED_X: that kernel, with or
+ * without the SiLU-mul epilogue, M <= 32, no norm prologue; AWQ_ERR_BAD_VARIANT where it cannot run. */
+int awq_aux_gemv_repacked_fused_ex(const void* x, int64_t ldx, const void* packed, void* y, int64_t M, int64_t K, int64_t N,
+                                   int64_t group_size, int dtype, const void* norm_h, const void* norm_delta, const void* norm_w,
+                                   void* norm_h_out, float norm_eps, int silu_mul, int variant, void* stream);
+
 /* AWQ-MoE decode step (the reference's AWQMoEMethod, python/sglang/srt/layers/quantization/awq.py:661-852, runs
  * NVIDIA Marlin MoE kernels; on ROCm it falls back to moe_wna16's Triton path).  `slots` independent one-row GEMVs in ONE launch:
  * slot s multiplies activation row s / x_div of x (row stride ldx) with the repacked weight of expert expert_ids[s] —

@@ -140,13 +140,29 @@ int awq_gemm_repacked(const void* x, int64_t ldx, const void* packed, const void
  *   33 rows and up where the MFMA tiling leaves most CUs without a tile (narrow or deep matrices, up to a few hundred rows): the tile
  *     kernel runs with K split over workgroups, fp32 partial tiles go to the scratch and a second small launch adds them in slice order,
  *     adds the bias and rounds once (11008 x 4096 at 128 rows: 89 -> 26 us).
- * Both are deterministic; sums agree with the no-workspace routes to fp32 rounding, not bit for bit.  workspace == NULL or too small:
+ * Both are deterministic; sums agree with the no-workspace routes to fp32 rounding, not bit for bit.  The same holds for the
+ * shared-activation GEMV (AWQ_RP_SHARED_X below) against the kernels it replaces at 17 .. 32 rows: same per-element rounding of W, fp32
+ * accumulation and one final rounding, another fp32 summation order.  workspace == NULL or too small:
  * exactly awq_gemm_repacked.  awq_gemm_repacked_workspace_bytes returns 0 where the scratch would not be used (at most 4096 + 32 MiB).
  */
 size_t awq_gemm_repacked_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t group_size, int dtype);
 
 int awq_gemm_repacked_ws(const void* x, int64_t ldx, const void* packed, const void* bias, void* y, void* workspace,
                          size_t workspace_bytes, int64_t M, int64_t K, int64_t N, int64_t group_size, int dtype, void* stream);
+
+/*
+ * Same as awq_gemm_repacked_ws with the decode kernel forced (tests and A/B benchmarks).  variant:
+ *   AWQ_RP_AUTO      exactly awq_gemm_repacked_ws
+ *   AWQ_RP_SHARED_X  1 <= M <= 32, fp16, group_size % 128 == 0, N <= 32768, ldx % 8 == 0, x 16-byte aligned: one strip of column
+ *                    groups per workgroup; the activations are loaded once per workgroup into LDS in MFMA operand order and shared
+ *                    by all its waves, which split the strip's (k-block, column group) units.  No workspace is used.
+ * Returns AWQ_ERR_BAD_VARIANT for an unknown variant or a shape / dtype outside the variant's domain; nothing is launched then.
+ */
+enum awq_repacked_variant { AWQ_RP_AUTO = 0, AWQ_RP_SHARED_X = 1 };
+
+int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const void* bias, void* y, void* workspace,
+                         size_t workspace_bytes, int64_t M, int64_t K, int64_t N, int64_t group_size, int dtype, int variant,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,16 +28,18 @@ EXPORTS = (
     "awq_gemm_repacked",
     "awq_gemm_repacked_workspace_bytes",
     "awq_gemm_repacked_ws",
+    "awq_gemm_repacked_ex",
 )
 # include/awq_aux.h (decode-harness helpers, not part of the operator boundary)
 AUX_EXPORTS = ("awq_aux_add_rmsnorm", "awq_aux_decode_attention", "awq_aux_decode_attention_workspace_bytes",
                "awq_aux_argmax_advance", "awq_aux_silu_mul",
-               "awq_aux_gemv_repacked_fused", "awq_aux_moe_gemv", "awq_aux_moe_gemv_blocks", "awq_aux_moe_align_blocks",
+               "awq_aux_gemv_repacked_fused", "awq_aux_gemv_repacked_fused_ex", "awq_aux_moe_gemv", "awq_aux_moe_gemv_blocks", "awq_aux_moe_align_blocks",
                "awq_aux_moe_align_blocks_n", "awq_aux_moe_gemm_blocks", "awq_aux_moe_sum")
 ABI_VERSION = 2
 
 DTYPE_F16, DTYPE_BF16, DTYPE_F32 = 0, 1, 2
 GEMM_AUTO, GEMM_GENERIC, GEMM_SKINNY, GEMM_TILED = 0, 1, 2, 3
+RP_AUTO, RP_SHARED_X = 0, 1          # enum awq_repacked_variant
 
 
 
@@ -86,6 +88,8 @@ def _bind(L):
     L.awq_gemm_repacked_workspace_bytes.restype = ctypes.c_size_t
     L.awq_gemm_repacked_ws.argtypes = [vp, i64, vp, vp, vp, vp, ctypes.c_size_t, i64, i64, i64, i64, ci, vp]
     L.awq_gemm_repacked_ws.restype = ci
+    L.awq_gemm_repacked_ex.argtypes = [vp, i64, vp, vp, vp, vp, sz, i64, i64, i64, i64, ci, ci, vp]
+    L.awq_gemm_repacked_ex.restype = ci
     L.awq_aux_add_rmsnorm.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.c_float, vp]
     L.awq_aux_add_rmsnorm.restype = ci
     L.awq_aux_decode_attention.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, ctypes.c_float, ci, vp, sz, vp]
@@ -94,6 +98,8 @@ def _bind(L):
     L.awq_aux_decode_attention.restype = ci
     L.awq_aux_gemv_repacked_fused.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, ci, vp, vp, vp, vp, ctypes.c_float, ci, vp]
     L.awq_aux_gemv_repacked_fused.restype = ci
+    L.awq_aux_gemv_repacked_fused_ex.argtypes = [vp, i64, vp, vp, i64, i64, i64, i64, ci, vp, vp, vp, vp, ctypes.c_float, ci, ci, vp]
+    L.awq_aux_gemv_repacked_fused_ex.restype = ci
     L.awq_aux_moe_gemv.argtypes = [vp, i64, ci, vp, i64, i64, vp, vp, vp, i64, i64, i64, i64, ci, ci, vp]
     L.awq_aux_moe_gemv.restype = ci
     L.awq_aux_moe_gemv_blocks.argtypes = [vp, i64, ci, vp, i64, vp, vp, i64, vp, vp, i64, i64, i64, ci, ci, vp]

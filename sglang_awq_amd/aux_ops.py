@@ -115,10 +115,11 @@ def interleave_gate_up(qweight: torch.Tensor, scales: torch.Tensor, qzeros: torc
 
 
 def gemv_repacked_fused(packed: torch.Tensor, K: int, N: int, group_size: int, x: Optional[torch.Tensor] = None,
-                        norm: Optional[tuple] = None, silu_mul: bool = False):
+                        norm: Optional[tuple] = None, silu_mul: bool = False, variant: int = _lib.RP_AUTO):
     """Repacked decode GEMV with RMSNorm(+residual) prologue and / or SiLU-mul epilogue (include/awq_aux.h).
     norm = (h, delta, weight, eps): returns (y, h + delta); else x is the input and (y, None) is returned.
-    Returns None when there is no fused kernel for the shape (callers run the separate ops)."""
+    Returns None when there is no fused kernel for the shape (callers run the separate ops).
+    variant (tests, A/B): _lib.RP_SHARED_X forces the shared-activation kernel (awq_aux_gemv_repacked_fused_ex)."""
     src = norm[0] if norm is not None else x
     assert src is not None and src.dtype == torch.float16 and src.dim() == 2 and src.is_contiguous() and src.shape[1] == K
     M = src.shape[0]
@@ -135,8 +136,12 @@ def gemv_repacked_fused(packed: torch.Tensor, K: int, N: int, group_size: int, x
         args = (_vp(h), _vp(delta), _vp(w), _vp(h_out), float(eps))
     else:
         args = (None, None, None, None, 0.0)
-    rc = _lib.load().awq_aux_gemv_repacked_fused(_vp(x), K, _vp(packed), _vp(y), M, K, N, group_size, _lib.DTYPE_F16, *args,
-                                                 1 if silu_mul else 0, _stream(src))
+    if variant != _lib.RP_AUTO:
+        rc = _lib.load().awq_aux_gemv_repacked_fused_ex(_vp(x), K, _vp(packed), _vp(y), M, K, N, group_size, _lib.DTYPE_F16, *args,
+                                                        1 if silu_mul else 0, int(variant), _stream(src))
+    else:
+        rc = _lib.load().awq_aux_gemv_repacked_fused(_vp(x), K, _vp(packed), _vp(y), M, K, N, group_size, _lib.DTYPE_F16, *args,
+                                                     1 if silu_mul else 0, _stream(src))
     if rc == _lib.ERR_BAD_VARIANT:
         return None
     _lib.check(rc, "awq_aux_gemv_repacked_fused")

@@ -26,6 +26,18 @@ bool pow2_le32(int v) { return v >= 1 && v <= 32 && (v & (v - 1)) == 0; }
 
 // Kernel choice on the fragment-major layout, shared by awq_gemm_repacked and the op's on-the-fly re-layout (so the two
 // routes give bit-identical results).  The table of routes and the measurements behind every threshold: awq_dispatch.h.
+// One launch of the decode GEMV for <= 32 rows without a workspace: the shared-activation kernel where awq_dispatch.h routes the
+// shape to it (route::sharedx_wins), else the per-wave-k-range family.  Also what a pass of the 33 .. 160-row route runs.
+static int gemv_one_launch(const GemmArgs& a, const void* packed, bool splitk_scratch) {
+  static const int env_sx = lab_env("AWQ_SHAREDX", -1);   // lab knob: 0 = never (the previous route), 1 = wherever its domain allows
+  const bool sx = env_sx < 0 ? route::sharedx_wins(a.M, a.K, a.N, splitk_scratch) : env_sx != 0;
+  if (sx) {
+    const int rs = launch_gemv_repacked_sharedx(a, packed, false);
+    if (rs != AWQ_ERR_BAD_VARIANT) return rs;
+  }
+  return launch_gemv_repacked(a, packed);
+}
+
 static int repacked_dispatch(const GemmArgs& a, const void* packed) {
   const int64_t M = a.M;
   // <= 32 rows: the streaming GEMV.  A few passes of it (32 rows each) beat the MFMA tiles while those leave most CUs idle and
@@ -35,11 +47,13 @@ static int repacked_dispatch(const GemmArgs& a, const void* packed) {
   // chip better (11008 x 4096 at M = 256: 142 -> 90 us); beyond that the hand-pipelined wide tiles.
   static const int env_mid = lab_env("AWQ_MID", 1);      // lab knob: 0 = never the 128 x 64 tiles
   if (M <= route::kGemvMaxRows) {
-    if (M >= route::kSplitKMinRows && a.workspace != nullptr) {             // narrow matrix, many rows: wide strips with K split across workgroups
+    static const int env_sx = lab_env("AWQ_SHAREDX", -1);
+    const bool sx_first = env_sx < 0 ? route::sharedx_wins(M, a.K, a.N, a.workspace != nullptr) : env_sx != 0;
+    if (!sx_first && M >= route::kSplitKMinRows && a.workspace != nullptr) {   // narrow matrix, many rows: wide strips with K split across workgroups
       const int rs = launch_gemv_repacked_splitk(a, packed);
       if (rs != AWQ_ERR_BAD_VARIANT) return rs;
     }
-    const int rc = launch_gemv_repacked(a, packed);
+    const int rc = gemv_one_launch(a, packed, a.workspace != nullptr);
     if (rc != AWQ_ERR_BAD_VARIANT || M <= 16) return rc;
     // 17..32 rows on a strip whose two-row-tile reduction scratch does not fit the CU's LDS: two passes of <= 16 rows
     GemmArgs c = a;
@@ -69,7 +83,7 @@ static int repacked_dispatch(const GemmArgs& a, const void* packed) {
       c.M = (int)(M - m0 < route::kGemvPassRows ? M - m0 : route::kGemvPassRows);
       c.x = (const char*)a.x + (size_t)m0 * a.ldx * eb2;
       c.y = (char*)a.y + (size_t)m0 * a.N * eb2;
-      const int rc = launch_gemv_repacked(c, packed);
+      const int rc = gemv_one_launch(c, packed, false);
       if (rc) return rc;
     }
     return AWQ_OK;
@@ -231,6 +245,25 @@ int awq_gemm_repacked_ws(const void* x, int64_t ldx, const void* packed, const v
   a.M = (int)M; a.K = (int)K; a.N = (int)N; a.g = (int)group_size; a.dtype = dtype; a.tune = 0;
   a.stream = (hipStream_t)stream;
   return repacked_dispatch(a, packed);
+}
+
+int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const void* bias, void* y, void* workspace,
+                         size_t workspace_bytes, int64_t M, int64_t K, int64_t N, int64_t group_size, int dtype, int variant,
+                         void* stream) {
+  if (variant == AWQ_RP_AUTO) return awq_gemm_repacked_ws(x, ldx, packed, bias, y, workspace, workspace_bytes, M, K, N, group_size, dtype, stream);
+  if (variant != AWQ_RP_SHARED_X) return AWQ_ERR_BAD_VARIANT;
+  if (!packed) return AWQ_ERR_NULL_POINTER;
+  if (K <= 0 || N <= 0 || group_size <= 0 || N % 8 || K % group_size || M < 0 || ldx < K) return AWQ_ERR_BAD_SHAPE;
+  if (M == 0) return AWQ_OK;
+  if (!x || !y) return AWQ_ERR_NULL_POINTER;
+  if ((((uintptr_t)packed) & 15) || (((uintptr_t)y) & 1)) return AWQ_ERR_MISALIGNED;
+  if (M > route::kGemvMaxRows) return AWQ_ERR_BAD_VARIANT;
+  GemmArgs a;
+  a.x = x; a.ldx = ldx; a.qweight = nullptr; a.scales = nullptr; a.qzeros = nullptr; a.bias = bias; a.y = y;
+  a.workspace = nullptr; a.workspace_bytes = 0;          // the kernel uses none
+  a.M = (int)M; a.K = (int)K; a.N = (int)N; a.g = (int)group_size; a.dtype = dtype; a.tune = 0;
+  a.stream = (hipStream_t)stream;
+  return launch_gemv_repacked_sharedx(a, packed, false);
 }
 
 }  // extern "C"

@@ -13,6 +13,9 @@
 //                                                                                                         slower at 6..12 rows and on wide strips (r03_kbench_rp3_ab.txt)
 //  9..32         K >= 8192 and N <= 4096, workspace given  gemv_rps_kernel (K split over workgroups)      11008 x 4096 at 12 / 16 / 32 rows 12.2 -> 10.6 / 14.7 -> 11.3 /
 //                                                                                                         23.1 -> 17.2; not at K = 4096 or N = 8192 (r02_kbench_splitk_ab.txt)
+//  17..32        N <= 32768; from 17 / 24 / 28 rows by strip    gemv_sharedx_kernel (x once per workgroup in    4096 x 22016 at 32 rows 20.7 -> 18.4; 4096 x 4096 10.6 -> 8.6; 11008 x 4096
+//                width (kSharedXMinRows), not 5-group strips   LDS in MFMA order, waves split the units)      22.9 -> 19.5; 4096 x 12288 13.6 -> 13.2; 8192 x 1280 17.4 -> 12.6
+//                                                                                                         (kbench_sharedx_ab.txt)
 //  2..32 (rest)  anything else, N <= 32768                 gemv_repacked_kernel (round 1: 8 / 16 waves,    17..32 rows: two row tiles per fragment, 8 waves
 //                                                          straight-line or double-buffered loop)
 //  1..32         N > 32768                                 gemv_repacked_kernel, rounds of 3-group strips  8192 x 57344: 145 -> 51 (G = 3; 53 / 54.5 / 60 at G = 2 / 4 / 1)
@@ -77,6 +80,35 @@ constexpr int kRp3MaxGroups = 2;                  // ... on strips of at most th
 constexpr int kRpsMinKBlocks = 64;                // K >= 8192
 constexpr int kRpsMaxGroups = 256;                // N <= 4096
 constexpr int kRpsStripGroups = 2;
+
+// ---- shared-activation GEMV (awq_repacked_sharedx.hip; awq_capi.hip: repacked_dispatch, awq_repacked_fused.hip)
+// First row count at which it measured faster than the two-row-tile gemv_repacked_kernel by more than the spread of repeated runs
+// (0.5 %), per strip width G = ceil(ceil(N / 16) / 256); kSharedXNever where it did not (profiles/kbench_sharedx_ab.txt, us old -> new):
+//   G = 1 from 24: 4096 x 4096 8.96 -> 8.22, 11008 x 4096 19.5 -> 18.1 (17 rows: 16.0 -> 17.1, not taken)
+//   G = 2 from 24: 8192 x 7168 16.9 -> 16.2 (17 rows: 14.4 -> 15.1), 3584 x 8192 10.6 -> 9.9, 4096 x 8192 11.0 -> 10.4
+//   G = 3 from 28: 4096 x 12288 13.05 -> 12.85, at 32 rows 13.6 -> 13.2 (24 rows: 12.27 -> 12.33)
+//   G = 4 from 17: 4096 x 16384 13.8 -> 13.6;  G = 5 never: 4096 x 20480 at 32 rows 18.0 -> 18.4 (15 waves of 3 k-block slots)
+//   G = 6, 7, 8 from 17: 4096 x 22016 17.8 -> 17.4 (32 rows 20.7 -> 18.4), 4096 x 28672 21.7 -> 20.3, 4096 x 32768 23.8 -> 21.6
+constexpr int kSharedXMaxRows = 32;               // its x buffers hold two row tiles
+constexpr int kSharedXNever = kSharedXMaxRows + 1;
+constexpr int kSharedXMinRows[kOneStripMaxGroups + 1] = {kSharedXNever, 24, 24, 28, 17, kSharedXNever, 17, 17, 17};
+// Where a workspace makes gemv_rps_kernel available (K >= 8192, N <= 4096) that one stays (11008 x 4096 at 32 rows: 16.7 against 19.5)
+// except on matrices of at most this many column groups, from 17 rows (8192 x 1280 at 17 / 32 rows: 12.8 -> 11.2 / 14.2 -> 12.6)
+constexpr int kSharedXOverSplitKMaxGroups = 80;
+constexpr int kSharedXOverSplitKMinRows = 17;
+constexpr int kSharedXSiluGroups = 6;             // SiLU-mul epilogue: measured on 6-group strips only (4096 x 22016 at 17 / 32 rows 17.7 -> 17.3 / 20.6 -> 18.2)
+// Pure functions of the shape and of whether a split-K scratch was given: the same call always takes the same route.
+inline bool sharedx_wins(int64_t M, int64_t K, int64_t N, bool splitk_scratch) {
+  const int64_t NG = (N + 15) / 16, KB = K / 128, G = (NG + 255) / 256;
+  if (M > kSharedXMaxRows || G > kOneStripMaxGroups) return false;
+  if (splitk_scratch && KB >= kRpsMinKBlocks && NG <= kRpsMaxGroups && NG >= 8)   // rps_plan's domain
+    return NG <= kSharedXOverSplitKMaxGroups && M >= kSharedXOverSplitKMinRows;
+  return M >= kSharedXMinRows[G];
+}
+inline bool sharedx_wins_silu(int64_t M, int64_t N) {
+  const int64_t NG = (N + 15) / 16;
+  return M >= kSharedXMinRows[kSharedXSiluGroups] && M <= kSharedXMaxRows && (NG + 255) / 256 == kSharedXSiluGroups;
+}
 
 // ---- prefill tile model (awq_repacked_prefill.hip), in rounds of the 256 CUs
 constexpr double kNarrowRound192 = 0.84;          // a round of 128 x 192 tiles / a round of 128 x 256 tiles (62 vs 73.5 us at K = 4096)

@@ -82,6 +82,8 @@ int launch_repack(const int32_t* qweight, const void* scales, const int32_t* qze
 int launch_gemv_repacked(const GemmArgs& a, const void* packed);
 bool gemv_strip_geometry(int64_t K, int64_t N, int* G, int* nwg);          // strip width / workgroups of the one-strip-per-workgroup decode GEMV; false: rounds mode
 int launch_gemv_repacked_loop(const GemmArgs& a, const void* packed);    // loop form of the straight-line GEMV: deep K, 9..16 rows on deep matrices (awq_repacked_loop.hip)
+// up to 32 rows, x staged once per workgroup in LDS in MFMA A-fragment order (awq_repacked_sharedx.hip); BAD_VARIANT outside fp16 / g % 128 == 0 / N <= 32768
+int launch_gemv_repacked_sharedx(const GemmArgs& a, const void* packed, bool silu_mul);
 int launch_gemv_repacked_fused(const GemmArgs& a, const void* packed);   // norm prologue and / or SiLU-mul epilogue (awq_repacked_fused.hip)
 int launch_gemv_repacked_moe(const GemmArgs& a, const void* packed);     // expert-indirect M = 1 GEMVs, one grid row per (token, expert) slot
 int launch_gemm_repacked_tiled(const GemmArgs& a, const void* packed);   // any M, MFMA-bound prefill shapes

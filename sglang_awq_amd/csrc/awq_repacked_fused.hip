@@ -24,6 +24,11 @@ int launch_gemv_repacked_fused(const GemmArgs& a, const void* packed) {
   if (!repacked_fast(a.K, a.N, a.g, a.dtype) || a.M < 1 || a.M > 32 || a.ldx % 8) return AWQ_ERR_BAD_VARIANT;   // fp16, g % 128 == 0 only
   if (a.M > 16) {                                                            // two row tiles: SiLU-mul epilogue only, 8 waves
     if (norm || !a.silu_mul || a.N % 32 || (((uintptr_t)a.x) & 15)) return AWQ_ERR_BAD_VARIANT;
+    static const int env_sx = lab_env("AWQ_SHAREDX", -1);                    // lab knob, as in awq_capi.hip
+    if (env_sx < 0 ? route::sharedx_wins_silu(a.M, a.N) : env_sx != 0) {   // x shared through LDS (awq_repacked_sharedx.hip)
+      const int rs = launch_gemv_repacked_sharedx(a, packed, true);
+      if (rs != AWQ_ERR_BAD_VARIANT) return rs;
+    }
     const int NG2 = rp_groups(a.N), KB2 = a.K / 128;
     int G2 = (NG2 + 255) / 256;
     if (G2 & 1) ++G2;
@@ -108,9 +113,9 @@ extern "C" int awq_aux_moe_gemv(const void* x, int64_t ldx, int x_div, const voi
   return awq::launch_gemv_repacked_moe(a, packed_experts);
 }
 
-extern "C" int awq_aux_gemv_repacked_fused(const void* x, int64_t ldx, const void* packed, void* y, int64_t M, int64_t K, int64_t N,
-                                           int64_t group_size, int dtype, const void* norm_h, const void* norm_delta,
-                                           const void* norm_w, void* norm_h_out, float norm_eps, int silu_mul, void* stream) {
+extern "C" int awq_aux_gemv_repacked_fused_ex(const void* x, int64_t ldx, const void* packed, void* y, int64_t M, int64_t K, int64_t N,
+                                              int64_t group_size, int dtype, const void* norm_h, const void* norm_delta,
+                                              const void* norm_w, void* norm_h_out, float norm_eps, int silu_mul, int variant, void* stream) {
   if (!packed || !y || (!x && !norm_h)) return AWQ_ERR_NULL_POINTER;
   if (K <= 0 || N <= 0 || group_size <= 0 || N % 8 || K % group_size || M <= 0 || ldx < K) return AWQ_ERR_BAD_SHAPE;
   if ((((uintptr_t)packed) & 15) || (((uintptr_t)y) & 1)) return AWQ_ERR_MISALIGNED;
@@ -121,5 +126,14 @@ extern "C" int awq_aux_gemv_repacked_fused(const void* x, int64_t ldx, const voi
   a.stream = (hipStream_t)stream;
   a.norm_h = norm_h; a.norm_delta = norm_delta; a.norm_w = norm_w; a.norm_h_out = norm_h_out; a.norm_eps = norm_eps;
   a.silu_mul = silu_mul;
-  return awq::launch_gemv_repacked_fused(a, packed);
+  if (variant == AWQ_RP_AUTO) return awq::launch_gemv_repacked_fused(a, packed);
+  if (variant != AWQ_RP_SHARED_X || norm_h != nullptr) return AWQ_ERR_BAD_VARIANT;
+  return awq::launch_gemv_repacked_sharedx(a, packed, silu_mul != 0);
+}
+
+extern "C" int awq_aux_gemv_repacked_fused(const void* x, int64_t ldx, const void* packed, void* y, int64_t M, int64_t K, int64_t N,
+                                           int64_t group_size, int dtype, const void* norm_h, const void* norm_delta,
+                                           const void* norm_w, void* norm_h_out, float norm_eps, int silu_mul, void* stream) {
+  return awq_aux_gemv_repacked_fused_ex(x, ldx, packed, y, M, K, N, group_size, dtype, norm_h, norm_delta, norm_w, norm_h_out, norm_eps,
+                                        silu_mul, AWQ_RP_AUTO, stream);
 }

@@ -368,9 +368,11 @@ def check_packed(packed: torch.Tensor, K: int, N: int, group_size: int, dev: tor
 
 
 def awq_gemm_repacked(input: torch.Tensor, packed: torch.Tensor, K: int, N: int, group_size: int,
-                      bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      bias: Optional[torch.Tensor] = None, variant: int = _lib.RP_AUTO) -> torch.Tensor:
     """y = input @ W (+ bias) from the repacked copy, any M, in the dtype of `input` — fp16 or bf16, which must be the dtype of
-    the scales the copy was made from (the copy stores their bits).  Same numerics as awq_gemm / awq_linear."""
+    the scales the copy was made from (the copy stores their bits).  Same numerics as awq_gemm / awq_linear.
+    variant (tests, A/B): _lib.RP_SHARED_X forces the shared-activation decode kernel (include/awq_hip.h: awq_gemm_repacked_ex)
+    and raises AwqHipError where it cannot run."""
     dt = input.dtype
     if input.dim() != 2 or input.shape[1] != K or dt not in (torch.float16, torch.bfloat16):
         raise RuntimeError(f"awq_gemm_repacked: input must be fp16 / bf16 [M, {K}], got {input.dtype} {tuple(input.shape)}")
@@ -386,7 +388,10 @@ def awq_gemm_repacked(input: torch.Tensor, packed: torch.Tensor, K: int, N: int,
     with _on_device(dev):
         y = torch.empty((M, N), dtype=dt, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if M > 8 and lib.awq_gemm_repacked_workspace_bytes(M, K, N, group_size, _DTYPE_CODE[dt]):
+        if variant != _lib.RP_AUTO:
+            rc = lib.awq_gemm_repacked_ex(_vp(input), ldx, _vp(packed), _vp(bias), _vp(y), None, 0, M, K, N, group_size, _DTYPE_CODE[dt],
+                                          int(variant), ctypes.c_void_p(stream))
+        elif M > 8 and lib.awq_gemm_repacked_workspace_bytes(M, K, N, group_size, _DTYPE_CODE[dt]):
             # 9 .. 32 rows on a narrow matrix (split-K GEMV) or 33 rows up with few MFMA tiles (split-K tiles): both want the
             # per-(device, stream) scratch (counters + fp32 partials)
             ws = _workspace(dev, stream)

@@ -291,12 +291,13 @@ static int cmd_stamps(int argc, char** argv) {
 
 // decode GEMV on the repacked (MFMA-fragment-major) layout
 static int cmd_rgemm(int argc, char** argv) {
-  if (argc < 6) { fprintf(stderr, "usage: kbench rgemm M K N g [sets] [iters] [graph] [fuse: 1 norm prologue, 2 silu-mul epilogue, 3 both]\n"); return 2; }
+  if (argc < 6) { fprintf(stderr, "usage: kbench rgemm M K N g [sets] [iters] [graph] [fuse: 1 norm prologue, 2 silu-mul epilogue, 3 both] [variant: 0 auto, 1 shared-x]\n"); return 2; }
   const int M = atoi(argv[2]), K = atoi(argv[3]), N = atoi(argv[4]), g = atoi(argv[5]);
   const int sets = argc > 6 ? atoi(argv[6]) : 16;
   const int iters = argc > 7 ? atoi(argv[7]) : 400;
   const int use_graph = argc > 8 ? atoi(argv[8]) : 1;
   const int fuse = argc > 9 ? atoi(argv[9]) : 0;
+  const int variant = argc > 10 ? atoi(argv[10]) : AWQ_RP_AUTO;
   const size_t pbytes = awq_repacked_bytes(K, N, g, AWQ_DTYPE_F16);
   if (!pbytes) { fprintf(stderr, "shape not supported by the repacked path\n"); return 1; }
   hipStream_t st; CK(hipStreamCreate(&st));
@@ -331,9 +332,9 @@ static int cmd_rgemm(int argc, char** argv) {
   hipStream_t cur = st; void* ycur = y;
   auto launch = [&](int i) {
     if (nstreams > 1) { cur = (i & 1) ? st2 : st; ycur = (i & 1) ? y2 : y; }
-    int rc = fuse ? awq_aux_gemv_repacked_fused(x, K, packed[i % sets], y, M, K, N, g, AWQ_DTYPE_F16, (fuse & 1) ? x : nullptr, delta, nw, hout,
-                                                1e-5f, (fuse & 2) ? 1 : 0, cur)
-                  : awq_gemm_repacked_ws(x, K, packed[i % sets], nullptr, ycur, ws, ws_bytes, M, K, N, g, AWQ_DTYPE_F16, cur);
+    int rc = fuse ? awq_aux_gemv_repacked_fused_ex(x, K, packed[i % sets], y, M, K, N, g, AWQ_DTYPE_F16, (fuse & 1) ? x : nullptr, delta, nw, hout,
+                                                   1e-5f, (fuse & 2) ? 1 : 0, variant, cur)
+                  : awq_gemm_repacked_ex(x, K, packed[i % sets], nullptr, ycur, ws, ws_bytes, M, K, N, g, AWQ_DTYPE_F16, variant, cur);
     if (rc) { fprintf(stderr, "awq_gemm_repacked: %s\n", awq_hip_status_string(rc)); exit(1); }
   };
   for (int i = 0; i < 2 * sets; ++i) launch(i);
@@ -372,7 +373,7 @@ static int cmd_rgemm(int argc, char** argv) {
   }
   const double us = ms * 1e3;
   const double bytes = (double)K * N / 2 + (double)(K / g) * N / 2 + (double)(K / g) * N * 2 + (double)M * K * 2 + (double)M * N * 2;
-  printf("rgemm M=%d K=%d N=%d g=%d sets=%d graph=%d fuse=%d : %9.3f us  %8.1f GB/s (algorithmic)  %8.2f TFLOP/s\n", M, K, N, g, sets, use_graph, fuse, us,
+  printf("rgemm M=%d K=%d N=%d g=%d sets=%d graph=%d fuse=%d variant=%d : %9.3f us  %8.1f GB/s (algorithmic)  %8.2f TFLOP/s\n", M, K, N, g, sets, use_graph, fuse, variant, us,
          bytes / us / 1e3, 2.0 * M * K * N / us / 1e6);
   return 0;
 }
