@@ -156,9 +156,13 @@ int awq_gemm_repacked_ws(const void* x, int64_t ldx, const void* packed, const v
  *   AWQ_RP_SHARED_X  1 <= M <= 32, fp16, group_size % 128 == 0, N <= 32768, ldx % 8 == 0, x 16-byte aligned: one strip of column
  *                    groups per workgroup; the activations are loaded once per workgroup into LDS in MFMA operand order and shared
  *                    by all its waves, which split the strip's (k-block, column group) units.  No workspace is used.
+ *   AWQ_RP_SHARED_X_WIDE  33 <= M <= 64, fp16, group_size % 128 == 0, 8192 < N <= 32768 (strips of 3 .. 8 column groups),
+ *                    ldx % 8 == 0, ldx < 2^24, x 16-byte aligned, K / 128 < 4096: the same split with every dequantised weight
+ *                    fragment multiplied into three (M <= 48) or four row tiles and every activation fragment into two column
+ *                    groups.  No workspace is used.
  * Returns AWQ_ERR_BAD_VARIANT for an unknown variant or a shape / dtype outside the variant's domain; nothing is launched then.
  */
-enum awq_repacked_variant { AWQ_RP_AUTO = 0, AWQ_RP_SHARED_X = 1 };
+enum awq_repacked_variant { AWQ_RP_AUTO = 0, AWQ_RP_SHARED_X = 1, AWQ_RP_SHARED_X_WIDE = 2 };
 
 int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const void* bias, void* y, void* workspace,
                          size_t workspace_bytes, int64_t M, int64_t K, int64_t N, int64_t group_size, int dtype, int variant,

@@ -68,6 +68,26 @@ static int repacked_dispatch(const GemmArgs& a, const void* packed) {
   if (!repacked_fast(a.K, a.N, a.g, a.dtype)) return launch_gemm_repacked_tiled(a, packed);   // bf16 / g in {32, 64}: the generic tiles from 33 rows on
   const bool aligned = a.ldx % 8 == 0 && (((uintptr_t)a.x) & 15) == 0;
   const int64_t wide_tiles = ((M + 127) / 128) * ((a.N + 255) / 256);
+  static const int env_sxw = lab_env("AWQ_SHAREDX_WIDE", -1);   // lab knob: 0 = never (the previous route), 1 = wherever its domain allows
+  if (env_sxw < 0 ? route::sharedx_wide_wins(M, a.K, a.N) : env_sxw != 0) {
+    // 33 .. 64 rows on wide matrices: one launch, three or four row tiles per dequantised fragment (65 .. 128 rows under the lab
+    // knob only: passes of <= 64 rows, measured and not routed — awq_dispatch.h)
+    if (M <= route::kSharedXWideMaxRows) {
+      const int rs = launch_gemv_repacked_sharedx_wide(a, packed);
+      if (rs != AWQ_ERR_BAD_VARIANT) return rs;
+    } else if (env_sxw > 1 && M <= 2 * route::kSharedXWideMaxRows) {
+      GemmArgs c = a;
+      c.M = (int)(M + 1) / 2;
+      int rs = launch_gemv_repacked_sharedx_wide(c, packed);
+      if (rs == AWQ_OK) {
+        c.M = (int)M - c.M;
+        c.x = (const char*)a.x + (size_t)((M + 1) / 2) * a.ldx * 2;
+        c.y = (char*)a.y + (size_t)((M + 1) / 2) * a.N * 2;
+        rs = launch_gemv_repacked_sharedx_wide(c, packed);
+      }
+      if (rs != AWQ_ERR_BAD_VARIANT) return rs;
+    }
+  }
   static const int env_sk = lab_env("AWQ_PF_SK", 1);     // lab knob: 0 = never the split-K tile route
   if (env_sk != 0 && aligned && wide_tiles <= route::kPfSplitMaxWideTiles && M >= route::kPfSplitMinRows) {
     const int rs = launch_gemm_repacked_split_tiles(a, packed);      // under-filled tiles + workspace: K split over workgroups
@@ -251,19 +271,19 @@ int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const v
                          size_t workspace_bytes, int64_t M, int64_t K, int64_t N, int64_t group_size, int dtype, int variant,
                          void* stream) {
   if (variant == AWQ_RP_AUTO) return awq_gemm_repacked_ws(x, ldx, packed, bias, y, workspace, workspace_bytes, M, K, N, group_size, dtype, stream);
-  if (variant != AWQ_RP_SHARED_X) return AWQ_ERR_BAD_VARIANT;
+  if (variant != AWQ_RP_SHARED_X && variant != AWQ_RP_SHARED_X_WIDE) return AWQ_ERR_BAD_VARIANT;
   if (!packed) return AWQ_ERR_NULL_POINTER;
   if (K <= 0 || N <= 0 || group_size <= 0 || N % 8 || K % group_size || M < 0 || ldx < K) return AWQ_ERR_BAD_SHAPE;
   if (M == 0) return AWQ_OK;
   if (!x || !y) return AWQ_ERR_NULL_POINTER;
   if ((((uintptr_t)packed) & 15) || (((uintptr_t)y) & 1)) return AWQ_ERR_MISALIGNED;
-  if (M > route::kGemvMaxRows) return AWQ_ERR_BAD_VARIANT;
+  if (variant == AWQ_RP_SHARED_X && M > route::kGemvMaxRows) return AWQ_ERR_BAD_VARIANT;
   GemmArgs a;
   a.x = x; a.ldx = ldx; a.qweight = nullptr; a.scales = nullptr; a.qzeros = nullptr; a.bias = bias; a.y = y;
   a.workspace = nullptr; a.workspace_bytes = 0;          // the kernel uses none
   a.M = (int)M; a.K = (int)K; a.N = (int)N; a.g = (int)group_size; a.dtype = dtype; a.tune = 0;
   a.stream = (hipStream_t)stream;
-  return launch_gemv_repacked_sharedx(a, packed, false);
+  return variant == AWQ_RP_SHARED_X ? launch_gemv_repacked_sharedx(a, packed, false) : launch_gemv_repacked_sharedx_wide(a, packed);
 }
 
 }  // extern "C"

@@ -19,6 +19,9 @@
 //  2..32 (rest)  anything else, N <= 32768                 gemv_repacked_kernel (round 1: 8 / 16 waves,    17..32 rows: two row tiles per fragment, 8 waves
 //                                                          straight-line or double-buffered loop)
 //  1..32         N > 32768                                 gemv_repacked_kernel, rounds of 3-group strips  8192 x 57344: 145 -> 51 (G = 3; 53 / 54.5 / 60 at G = 2 / 4 / 1)
+//  33..64        8192 < N <= 32768 (kSharedXWideMinRows3 / 4:   gemv_sharedx_wide_kernel (x once per workgroup   4096 x 22016 at 64 rows 35.4 -> 23.3 (a 32-row pass: 18.4); 4096 x 12288
+//                every strip width 3..8)                       in LDS, 3 / 4 row tiles per fragment, a wave     24.8 -> 17.6 (13.0); 8192 x 28672 75.1 -> 50.2 (38.7)
+//                                                              owns two column groups of a k-block)             (kbench_sharedx_wide_ab.txt)
 //  33..160       while passes cost less than the tiles     passes of <= 32 rows of the GEMV                a pass 10.3 / 13.2 / 19.7 / 22.8 us on 4096 x 4096 / x 11008 / x 22016 /
 //                (gemv_passes_max: 2..4 passes)                                                           11008 x 4096; under-filled tiles ~1.12 us per k-block: 37-44 / 91 us
 //                                                                                                         (r03_kbench_middle_rows_ab.txt: 4096 x 22016 at 128 rows 78.6 -> 44)
@@ -108,6 +111,31 @@ inline bool sharedx_wins(int64_t M, int64_t K, int64_t N, bool splitk_scratch) {
 inline bool sharedx_wins_silu(int64_t M, int64_t N) {
   const int64_t NG = (N + 15) / 16;
   return M >= kSharedXMinRows[kSharedXSiluGroups] && M <= kSharedXMaxRows && (NG + 255) / 256 == kSharedXSiluGroups;
+}
+
+// ---- shared-activation GEMV for 33 .. 64 rows on wide matrices (awq_repacked_sharedx_wide.hip; awq_capi.hip: repacked_dispatch)
+// Routed per (strip width G, row-tile count) where it measured faster than the parent route (passes of the 32-row GEMV or under-filled
+// tiles; the same with a workspace: no split-K route applies on these widths) by more than the spread of repeated runs (<= 0.5 us,
+// 1.5 %).  Every cell won (profiles/kbench_sharedx_wide_ab.txt, us old -> new at 33 / 48 rows | 49 / 64 rows; a 32-row pass beside it):
+//   G = 3  4096 x 12288: 18.8 -> 13.8 / 21.3 -> 15.0 | 23.3 -> 16.6 / 24.8 -> 17.6   (13.0)
+//   G = 4  4096 x 16384: 21.9 -> 15.0 / 24.5 -> 16.4 | 27.0 -> 17.3 / 28.3 -> 18.9   (14.9)
+//   G = 5  4096 x 20480: 26.1 -> 18.0 / 30.5 -> 19.8 | 32.3 -> 21.6 / 34.2 -> 23.1   (17.6)
+//   G = 6  4096 x 22016: 27.7 -> 18.6 / 32.8 -> 20.0 | 34.3 -> 21.8 / 35.4 -> 23.3   (18.4)
+//   G = 7  4096 x 28672: 39.0 -> 22.8 / 39.3 -> 24.6 | 39.4 -> 27.4 / 39.5 -> 28.8   (22.1); 8192 x 28672: 59.7 -> 40.0 / 63.7 -> 43.0 | 70.3 -> 47.3 / 75.1 -> 50.2 (38.7)
+//   G = 8  4096 x 32768: 40.3 -> 24.0 / 40.5 -> 25.7 | 40.6 -> 28.0 / 41.0 -> 29.5   (22.9)
+// Not routed: 65 .. 128 rows as two passes of it (4096 x 22016 at 96 / 128 rows 39.0 -> 38.1 / 39.6 -> 44.4; 4096 x 12288 with a
+// workspace 26.5 -> 28.7 / 29.0 -> 33.6): inside the spread or slower.
+constexpr int kSharedXWideMinRows = 33;
+constexpr int kSharedXWideMaxRows = 64;           // four row tiles
+constexpr int kSharedXWideNever = kSharedXWideMaxRows + 1;
+// first row count per strip width G from which it is routed, for three (33 .. 48) and four (49 .. 64) row tiles
+constexpr int kSharedXWideMinRows3[kOneStripMaxGroups + 1] = {kSharedXWideNever, kSharedXWideNever, kSharedXWideNever, 33, 33, 33, 33, 33, 33};
+constexpr int kSharedXWideMinRows4[kOneStripMaxGroups + 1] = {kSharedXWideNever, kSharedXWideNever, kSharedXWideNever, 49, 49, 49, 49, 49, 49};
+inline bool sharedx_wide_wins(int64_t M, int64_t K, int64_t N) {
+  const int64_t NG = (N + 15) / 16, G = (NG + 255) / 256;
+  (void)K;
+  if (M < kSharedXWideMinRows || M > kSharedXWideMaxRows || G > kOneStripMaxGroups) return false;
+  return M <= 48 ? M >= kSharedXWideMinRows3[G] : M >= kSharedXWideMinRows4[G];
 }
 
 // ---- prefill tile model (awq_repacked_prefill.hip), in rounds of the 256 CUs

@@ -84,6 +84,8 @@ bool gemv_strip_geometry(int64_t K, int64_t N, int* G, int* nwg);          // st
 int launch_gemv_repacked_loop(const GemmArgs& a, const void* packed);    // loop form of the straight-line GEMV: deep K, 9..16 rows on deep matrices (awq_repacked_loop.hip)
 // up to 32 rows, x staged once per workgroup in LDS in MFMA A-fragment order (awq_repacked_sharedx.hip); BAD_VARIANT outside fp16 / g % 128 == 0 / N <= 32768
 int launch_gemv_repacked_sharedx(const GemmArgs& a, const void* packed, bool silu_mul);
+// 33 .. 64 rows on strips of 3 .. 8 column groups, three or four row tiles per dequantised fragment (awq_repacked_sharedx_wide.hip); BAD_VARIANT outside
+int launch_gemv_repacked_sharedx_wide(const GemmArgs& a, const void* packed);
 int launch_gemv_repacked_fused(const GemmArgs& a, const void* packed);   // norm prologue and / or SiLU-mul epilogue (awq_repacked_fused.hip)
 int launch_gemv_repacked_moe(const GemmArgs& a, const void* packed);     // expert-indirect M = 1 GEMVs, one grid row per (token, expert) slot
 int launch_gemm_repacked_tiled(const GemmArgs& a, const void* packed);   // any M, MFMA-bound prefill shapes

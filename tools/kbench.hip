@@ -291,7 +291,7 @@ static int cmd_stamps(int argc, char** argv) {
 
 // decode GEMV on the repacked (MFMA-fragment-major) layout
 static int cmd_rgemm(int argc, char** argv) {
-  if (argc < 6) { fprintf(stderr, "usage: kbench rgemm M K N g [sets] [iters] [graph] [fuse: 1 norm prologue, 2 silu-mul epilogue, 3 both] [variant: 0 auto, 1 shared-x]\n"); return 2; }
+  if (argc < 6) { fprintf(stderr, "usage: kbench rgemm M K N g [sets] [iters] [graph] [fuse: 1 norm prologue, 2 silu-mul epilogue, 3 both] [variant: 0 auto, 1 shared-x, 2 shared-x wide]\n"); return 2; }
   const int M = atoi(argv[2]), K = atoi(argv[3]), N = atoi(argv[4]), g = atoi(argv[5]);
   const int sets = argc > 6 ? atoi(argv[6]) : 16;
   const int iters = argc > 7 ? atoi(argv[7]) : 400;
