@@ -160,9 +160,17 @@ int awq_gemm_repacked_ws(const void* x, int64_t ldx, const void* packed, const v
  *                    ldx % 8 == 0, ldx < 2^24, x 16-byte aligned, K / 128 < 4096: the same split with every dequantised weight
  *                    fragment multiplied into three (M <= 48) or four row tiles and every activation fragment into two column
  *                    groups.  No workspace is used.
+ *   AWQ_RP_SHARED_X_BF16  bf16, group_size % 128 == 0, ldx % 8 == 0, x 16-byte aligned, K / 128 < 4096: the bf16 form of
+ *                    AWQ_RP_SHARED_X, its dequantisation kept in fp32.  1 <= M <= 32 on N <= 32768: one launch (one row tile up to
+ *                    16 rows, two above); 33 <= M <= 64 on 8192 < N <= 32768: two launches of it (rows 0 .. 31, then the rest).
+ *                    Every weight is the bf16 awq_dequantize produces (for normal scales of magnitude >= 2^-122; see
+ *                    awq_repacked_sharedx_bf16.hip).  No workspace is used.  Not built: a bf16 form of AWQ_RP_SHARED_X_WIDE (three /
+ *                    four row tiles in one launch) gave wrong sums on the MI355X for a reason not found.
+ *                    AWQ_RP_SHARED_X and AWQ_RP_SHARED_X_WIDE refuse bf16; this variant refuses fp16.
  * Returns AWQ_ERR_BAD_VARIANT for an unknown variant or a shape / dtype outside the variant's domain; nothing is launched then.
+ * (Enumerators are only ever added: an added variant does not move AWQ_HIP_ABI_VERSION.)
  */
-enum awq_repacked_variant { AWQ_RP_AUTO = 0, AWQ_RP_SHARED_X = 1, AWQ_RP_SHARED_X_WIDE = 2 };
+enum awq_repacked_variant { AWQ_RP_AUTO = 0, AWQ_RP_SHARED_X = 1, AWQ_RP_SHARED_X_WIDE = 2, AWQ_RP_SHARED_X_BF16 = 3 };
 
 int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const void* bias, void* y, void* workspace,
                          size_t workspace_bytes, int64_t M, int64_t K, int64_t N, int64_t group_size, int dtype, int variant,

@@ -40,6 +40,15 @@ static int gemv_one_launch(const GemmArgs& a, const void* packed, bool splitk_sc
 
 static int repacked_dispatch(const GemmArgs& a, const void* packed) {
   const int64_t M = a.M;
+  // bf16, g % 128 == 0, up to 64 rows: the bf16 shared-activation kernels in the cells where they measured faster than the generic
+  // routes below (route::sharedx_bf16_wins)
+  if (a.dtype == AWQ_DTYPE_BF16 && a.g % 128 == 0 && M <= route::kSharedXBf16MaxRows) {
+    static const int env_sxb = lab_env("AWQ_SHAREDX_BF16", -1);   // lab knob: 0 = never (the previous route), 1 = wherever its domain allows
+    if (env_sxb < 0 ? route::sharedx_bf16_wins(M, a.K, a.N) : env_sxb != 0) {
+      const int rs = launch_gemv_repacked_sharedx_bf16(a, packed);
+      if (rs != AWQ_ERR_BAD_VARIANT) return rs;
+    }
+  }
   // <= 32 rows: the streaming GEMV.  A few passes of it (32 rows each) beat the MFMA tiles while those leave most CUs idle and
   // are bound by their K loop — how many, route::gemv_passes_max says (two on 4096 x 22016, three on 4096 x 11008, four on narrow
   // matrices; round 2 ran passes up to 160 rows everywhere: 4096 x 22016 at 128 rows 78.6 us against 44 on tiles).  Where the
@@ -271,7 +280,7 @@ int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const v
                          size_t workspace_bytes, int64_t M, int64_t K, int64_t N, int64_t group_size, int dtype, int variant,
                          void* stream) {
   if (variant == AWQ_RP_AUTO) return awq_gemm_repacked_ws(x, ldx, packed, bias, y, workspace, workspace_bytes, M, K, N, group_size, dtype, stream);
-  if (variant != AWQ_RP_SHARED_X && variant != AWQ_RP_SHARED_X_WIDE) return AWQ_ERR_BAD_VARIANT;
+  if (variant != AWQ_RP_SHARED_X && variant != AWQ_RP_SHARED_X_WIDE && variant != AWQ_RP_SHARED_X_BF16) return AWQ_ERR_BAD_VARIANT;
   if (!packed) return AWQ_ERR_NULL_POINTER;
   if (K <= 0 || N <= 0 || group_size <= 0 || N % 8 || K % group_size || M < 0 || ldx < K) return AWQ_ERR_BAD_SHAPE;
   if (M == 0) return AWQ_OK;
@@ -283,6 +292,7 @@ int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const v
   a.workspace = nullptr; a.workspace_bytes = 0;          // the kernel uses none
   a.M = (int)M; a.K = (int)K; a.N = (int)N; a.g = (int)group_size; a.dtype = dtype; a.tune = 0;
   a.stream = (hipStream_t)stream;
+  if (variant == AWQ_RP_SHARED_X_BF16) return launch_gemv_repacked_sharedx_bf16(a, packed);
   return variant == AWQ_RP_SHARED_X ? launch_gemv_repacked_sharedx(a, packed, false) : launch_gemv_repacked_sharedx_wide(a, packed);
 }
 

@@ -1,7 +1,8 @@
 // One place for the (M, K, N) -> kernel choices on the fragment-major layout and the measured crossover points behind them.
 // Every threshold the launchers use is a named constant here; the launchers (awq_capi.hip: repacked_dispatch; awq_repacked.hip:
 // launch_gemv_repacked; awq_repacked_splitk.hip: rps_plan; awq_repacked_prefill.hip: launch_gemm_repacked_pipelined) only apply them.
-// fp16, group size a multiple of 128 unless noted; bf16 and g in {32, 64} take the generic kernels of awq_repacked_ext.hip at every M.
+// fp16, group size a multiple of 128 unless noted; g in {32, 64} takes the generic kernels of awq_repacked_ext.hip at every M, and so does
+// bf16 except in the cells of the bf16 row below.
 //
 //  rows M        matrix                                   kernel                                        measured (us; source)
 //  ------------  ---------------------------------------  --------------------------------------------  ------------------------------------------------
@@ -22,6 +23,9 @@
 //  33..64        8192 < N <= 32768 (kSharedXWideMinRows3 / 4:   gemv_sharedx_wide_kernel (x once per workgroup   4096 x 22016 at 64 rows 35.4 -> 23.3 (a 32-row pass: 18.4); 4096 x 12288
 //                every strip width 3..8)                       in LDS, 3 / 4 row tiles per fragment, a wave     24.8 -> 17.6 (13.0); 8192 x 28672 75.1 -> 50.2 (38.7)
 //                                                              owns two column groups of a k-block)             (kbench_sharedx_wide_ab.txt)
+//  bf16 1..64    g % 128 == 0, N <= 32768: 17..32 rows on every   gemv_sharedx_bf16_kernel (the 32-row kernel's   4096 x 22016 at 16 / 32 / 64 rows 20.8 -> 18.7 / 40.8 -> 21.4 / 85.4 -> 41.5;
+//                strip width, 1..16 on 5- and 6-group strips,     structure, dequantisation in fp32; 33..64 rows  4096 x 4096 at 32 rows 13.3 -> 9.5 (kbench_sharedx_bf16_ab.txt)
+//                33..64 on N > 8192 (kSharedXBf16MinRows)         as two launches)
 //  33..160       while passes cost less than the tiles     passes of <= 32 rows of the GEMV                a pass 10.3 / 13.2 / 19.7 / 22.8 us on 4096 x 4096 / x 11008 / x 22016 /
 //                (gemv_passes_max: 2..4 passes)                                                           11008 x 4096; under-filled tiles ~1.12 us per k-block: 37-44 / 91 us
 //                                                                                                         (r03_kbench_middle_rows_ab.txt: 4096 x 22016 at 128 rows 78.6 -> 44)
@@ -136,6 +140,43 @@ inline bool sharedx_wide_wins(int64_t M, int64_t K, int64_t N) {
   (void)K;
   if (M < kSharedXWideMinRows || M > kSharedXWideMaxRows || G > kOneStripMaxGroups) return false;
   return M <= 48 ? M >= kSharedXWideMinRows3[G] : M >= kSharedXWideMinRows4[G];
+}
+
+// ---- bf16 shared-activation GEMV, 1 .. 64 rows (awq_repacked_sharedx_bf16.hip; awq_capi.hip: repacked_dispatch)
+// Routed per (row tiles, strip width G) where the forced kernel measured faster than the parent route (gemv_rpx_kernel in 16-row launches
+// on strips of at most 4 column groups; the generic 128 x 256 tiles from 33 rows) by more than the spread of repeated runs (median
+// 0.07 us, at most 0.7 us / 2.7 %).  profiles/kbench_sharedx_bf16_ab.txt, us old -> new, g = 128; every cell of the table was measured:
+//   1 .. 16 rows (at 1 / 8 / 16): routed on G = 5  4096 x 20480: 19.0 -> 16.1 / 19.6 -> 17.0 / 20.7 -> 17.4
+//                                       and G = 6  4096 x 22016: 19.0 -> 17.5 / 19.6 -> 18.1 / 20.8 -> 18.7
+//     lost, not routed: G = 1 4096 x 4096 4.9 -> 6.4 / 5.6 -> 6.8 / 6.8 -> 7.2, 11008 x 4096 10.1 -> 13.8 / 11.5 -> 14.2 / 15.4 -> 15.4 (inside the
+//     spread); G = 2 8192 x 7168 11.8 -> 13.3 / 12.0 -> 13.8 / 14.0 -> 15.1; G = 3 4096 x 12288 9.2 -> 10.7 / 9.8 -> 11.5 / 10.3 -> 12.1;
+//     G = 4 4096 x 16384 11.7 -> 12.9 / 11.8 -> 13.5 / 12.5 -> 14.0; G = 7 4096 x 28672 20.1 -> 21.5 / 21.0 -> 22.3 / 22.1 -> 22.6, 8192 x 28672
+//     36.5 -> 39.3 / 37.8 -> 40.1 / 39.6 -> 40.8; G = 8 4096 x 32768 21.6 -> 22.5 / 22.3 -> 23.1 / 23.1 -> 23.5
+//   17 .. 32 rows (at 17 / 24 / 32): routed on every G
+//     G = 1 4096 x 4096 11.2 -> 8.6 / 11.8 -> 9.1 / 13.3 -> 9.5, 11008 x 4096 25.0 -> 19.6 / 26.1 -> 20.4 / 30.2 -> 21.7; G = 2 8192 x 7168 24.9 -> 17.0 /
+//     25.4 -> 17.7 / 27.3 -> 18.5; G = 3 4096 x 12288 18.7 -> 13.5 / 19.5 -> 14.1 / 19.7 -> 14.6; G = 4 4096 x 16384 22.8 -> 15.5 / 23.1 -> 16.1 / 23.6 -> 16.6;
+//     G = 5 4096 x 20480 38.9 -> 19.5 / 39.6 -> 20.1 / 40.6 -> 20.8; G = 6 4096 x 22016 39.2 -> 20.4 / 39.9 -> 20.9 / 40.8 -> 21.4; G = 7 4096 x 28672
+//     40.7 -> 24.5 / 41.4 -> 25.3 / 42.5 -> 26.1, 8192 x 28672 75.1 -> 44.1 / 75.9 -> 45.6 / 77.9 -> 46.6; G = 8 4096 x 32768 43.2 -> 25.4 / 43.9 -> 25.9 / 44.0 -> 26.7
+//   33 .. 48 | 49 .. 64 rows (at 33 / 48 | 49 / 64; two launches of the kernel): routed on G = 3 .. 8, its whole domain
+//     G = 3 4096 x 12288 84.9 -> 24.4 / 85.1 -> 25.4 | 85.1 -> 27.0 / 85.3 -> 28.3; G = 4 4096 x 16384 84.9 -> 28.3 / 85.0 -> 29.3 | 84.9 -> 30.7 / 85.3 -> 31.8;
+//     G = 5 4096 x 20480 85.2 -> 35.2 / 85.3 -> 36.8 | 85.3 -> 38.9 / 85.3 -> 39.9; G = 6 4096 x 22016 85.1 -> 37.8 / 85.2 -> 38.9 | 85.2 -> 40.7 / 85.4 -> 41.5;
+//     G = 7 4096 x 28672 85.3 -> 45.7 / 85.3 -> 46.6 | 85.3 -> 48.1 / 85.7 -> 50.1, 8192 x 28672 162.5 -> 82.9 / 162.8 -> 84.9 | 162.9 -> 88.5 / 163.2 -> 91.1;
+//     G = 8 4096 x 32768 85.2 -> 47.0 / 85.5 -> 48.3 | 85.8 -> 49.7 / 85.9 -> 51.1
+// The fp16 shared-activation kernels on the same shapes: 18.4 us (32 rows) and 23.2 (64 rows, one launch with four row tiles) on 4096 x 22016.
+constexpr int kSharedXBf16MaxRows = 64;           // two launches of two row tiles
+constexpr int kSharedXBf16Never = kSharedXBf16MaxRows + 1;
+// first row count per (row tiles 1 .. 4, strip width G) from which it is routed, up to the last row of that tile count
+constexpr int kSharedXBf16MinRows[4][kOneStripMaxGroups + 1] = {
+    {kSharedXBf16Never, kSharedXBf16Never, kSharedXBf16Never, kSharedXBf16Never, kSharedXBf16Never, 1, 1, kSharedXBf16Never, kSharedXBf16Never},
+    {kSharedXBf16Never, 17, 17, 17, 17, 17, 17, 17, 17},
+    {kSharedXBf16Never, kSharedXBf16Never, kSharedXBf16Never, 33, 33, 33, 33, 33, 33},
+    {kSharedXBf16Never, kSharedXBf16Never, kSharedXBf16Never, 49, 49, 49, 49, 49, 49}};
+// A pure function of the shape: the same call always takes the same route.
+inline bool sharedx_bf16_wins(int64_t M, int64_t K, int64_t N) {
+  const int64_t NG = (N + 15) / 16, G = (NG + 255) / 256;
+  (void)K;
+  if (M < 1 || M > kSharedXBf16MaxRows || G > kOneStripMaxGroups) return false;
+  return M >= kSharedXBf16MinRows[(M - 1) / 16][G];
 }
 
 // ---- prefill tile model (awq_repacked_prefill.hip), in rounds of the 256 CUs

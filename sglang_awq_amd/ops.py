@@ -372,8 +372,9 @@ def awq_gemm_repacked(input: torch.Tensor, packed: torch.Tensor, K: int, N: int,
     """y = input @ W (+ bias) from the repacked copy, any M, in the dtype of `input` — fp16 or bf16, which must be the dtype of
     the scales the copy was made from (the copy stores their bits).  Same numerics as awq_gemm / awq_linear.
     variant (tests, A/B): _lib.RP_SHARED_X forces the shared-activation decode kernel (M <= 32), _lib.RP_SHARED_X_WIDE its form for
-    33 .. 64 rows on matrices wider than 8192 columns (include/awq_hip.h: awq_gemm_repacked_ex); either raises AwqHipError where
-    it cannot run."""
+    33 .. 64 rows on matrices wider than 8192 columns, _lib.RP_SHARED_X_BF16 the bf16 form of both (M <= 32, or 33 .. 64 rows on
+    matrices wider than 8192 columns; the fp16 variants refuse bf16 and this one refuses fp16) (include/awq_hip.h:
+    awq_gemm_repacked_ex); each raises AwqHipError where it cannot run."""
     dt = input.dtype
     if input.dim() != 2 or input.shape[1] != K or dt not in (torch.float16, torch.bfloat16):
         raise RuntimeError(f"awq_gemm_repacked: input must be fp16 / bf16 [M, {K}], got {input.dtype} {tuple(input.shape)}")

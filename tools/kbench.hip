@@ -291,38 +291,41 @@ static int cmd_stamps(int argc, char** argv) {
 
 // decode GEMV on the repacked (MFMA-fragment-major) layout
 static int cmd_rgemm(int argc, char** argv) {
-  if (argc < 6) { fprintf(stderr, "usage: kbench rgemm M K N g [sets] [iters] [graph] [fuse: 1 norm prologue, 2 silu-mul epilogue, 3 both] [variant: 0 auto, 1 shared-x, 2 shared-x wide]\n"); return 2; }
+  if (argc < 6) { fprintf(stderr, "usage: kbench rgemm M K N g [sets] [iters] [graph] [fuse: 1 norm prologue, 2 silu-mul epilogue, 3 both] [variant: 0 auto, 1 shared-x, 2 shared-x wide, 3 shared-x bf16] [dtype: 0 fp16, 1 bf16]\n"); return 2; }
   const int M = atoi(argv[2]), K = atoi(argv[3]), N = atoi(argv[4]), g = atoi(argv[5]);
   const int sets = argc > 6 ? atoi(argv[6]) : 16;
   const int iters = argc > 7 ? atoi(argv[7]) : 400;
   const int use_graph = argc > 8 ? atoi(argv[8]) : 1;
   const int fuse = argc > 9 ? atoi(argv[9]) : 0;
   const int variant = argc > 10 ? atoi(argv[10]) : AWQ_RP_AUTO;
-  const size_t pbytes = awq_repacked_bytes(K, N, g, AWQ_DTYPE_F16);
+  const int dtype = argc > 11 ? atoi(argv[11]) : AWQ_DTYPE_F16;
+  if (dtype != AWQ_DTYPE_F16 && dtype != AWQ_DTYPE_BF16) { fprintf(stderr, "rgemm: dtype 0 (fp16) or 1 (bf16)\n"); return 2; }
+  if (fuse && dtype != AWQ_DTYPE_F16) { fprintf(stderr, "rgemm: the fused forms are fp16 only\n"); return 2; }
+  const size_t pbytes = awq_repacked_bytes(K, N, g, dtype);
   if (!pbytes) { fprintf(stderr, "shape not supported by the repacked path\n"); return 1; }
   hipStream_t st; CK(hipStreamCreate(&st));
   std::vector<void*> packed(sets);
   {
-    auto w = make_weights(1, K, N, g, AWQ_DTYPE_F16);
+    auto w = make_weights(1, K, N, g, dtype);
     for (int i = 0; i < sets; ++i) {
       CK(hipMalloc(&packed[i], pbytes));
       fill_u32(w[0].qw, (size_t)K * N / 8);       // fresh random nibbles per set
-      int rc = awq_repack(w[0].qw, w[0].sc, w[0].qz, packed[i], K, N, g, AWQ_DTYPE_F16, st);
+      int rc = awq_repack(w[0].qw, w[0].sc, w[0].qz, packed[i], K, N, g, dtype, st);
       if (rc) { fprintf(stderr, "awq_repack: %s\n", awq_hip_status_string(rc)); return 1; }
       CK(hipStreamSynchronize(st));
     }
   }
   void *x, *y;
-  CK(hipMalloc(&x, (size_t)M * K * 2)); fill_scales(x, (size_t)M * K, AWQ_DTYPE_F16, -1.f, 1.f);
+  CK(hipMalloc(&x, (size_t)M * K * 2)); fill_scales(x, (size_t)M * K, dtype, -1.f, 1.f);
   CK(hipMalloc(&y, (size_t)M * N * 2));
   void *delta, *nw, *hout;
-  CK(hipMalloc(&delta, (size_t)M * K * 2)); fill_scales(delta, (size_t)M * K, AWQ_DTYPE_F16, -1.f, 1.f);
-  CK(hipMalloc(&nw, (size_t)K * 2)); fill_scales(nw, (size_t)K, AWQ_DTYPE_F16, 0.5f, 1.5f);
+  CK(hipMalloc(&delta, (size_t)M * K * 2)); fill_scales(delta, (size_t)M * K, dtype, -1.f, 1.f);
+  CK(hipMalloc(&nw, (size_t)K * 2)); fill_scales(nw, (size_t)K, dtype, 0.5f, 1.5f);
   CK(hipMalloc(&hout, (size_t)M * K * 2));
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   // optional scratch (the split-K route for 9..32 rows on narrow matrices): on unless KBENCH_WS=0
   void* ws = nullptr;
-  const size_t ws_bytes = (getenv("KBENCH_WS") && atoi(getenv("KBENCH_WS")) == 0) ? 0 : awq_gemm_repacked_workspace_bytes(M, K, N, g, AWQ_DTYPE_F16);
+  const size_t ws_bytes = (getenv("KBENCH_WS") && atoi(getenv("KBENCH_WS")) == 0) ? 0 : awq_gemm_repacked_workspace_bytes(M, K, N, g, dtype);
   if (ws_bytes) { CK(hipMalloc(&ws, ws_bytes)); CK(hipMemset(ws, 0, ws_bytes)); }
   // KBENCH_STREAMS=2 (probe): the launches of a graph alternate between two streams with no dependency between them — how much of the
   // per-launch boundary + ramp disappears when the next kernel may start before the previous one has drained
@@ -332,9 +335,9 @@ static int cmd_rgemm(int argc, char** argv) {
   hipStream_t cur = st; void* ycur = y;
   auto launch = [&](int i) {
     if (nstreams > 1) { cur = (i & 1) ? st2 : st; ycur = (i & 1) ? y2 : y; }
-    int rc = fuse ? awq_aux_gemv_repacked_fused_ex(x, K, packed[i % sets], y, M, K, N, g, AWQ_DTYPE_F16, (fuse & 1) ? x : nullptr, delta, nw, hout,
+    int rc = fuse ? awq_aux_gemv_repacked_fused_ex(x, K, packed[i % sets], y, M, K, N, g, dtype, (fuse & 1) ? x : nullptr, delta, nw, hout,
                                                    1e-5f, (fuse & 2) ? 1 : 0, variant, cur)
-                  : awq_gemm_repacked_ex(x, K, packed[i % sets], nullptr, ycur, ws, ws_bytes, M, K, N, g, AWQ_DTYPE_F16, variant, cur);
+                  : awq_gemm_repacked_ex(x, K, packed[i % sets], nullptr, ycur, ws, ws_bytes, M, K, N, g, dtype, variant, cur);
     if (rc) { fprintf(stderr, "awq_gemm_repacked: %s\n", awq_hip_status_string(rc)); exit(1); }
   };
   for (int i = 0; i < 2 * sets; ++i) launch(i);
@@ -373,7 +376,7 @@ static int cmd_rgemm(int argc, char** argv) {
   }
   const double us = ms * 1e3;
   const double bytes = (double)K * N / 2 + (double)(K / g) * N / 2 + (double)(K / g) * N * 2 + (double)M * K * 2 + (double)M * N * 2;
-  printf("rgemm M=%d K=%d N=%d g=%d sets=%d graph=%d fuse=%d variant=%d : %9.3f us  %8.1f GB/s (algorithmic)  %8.2f TFLOP/s\n", M, K, N, g, sets, use_graph, fuse, variant, us,
+  printf("rgemm M=%d K=%d N=%d g=%d sets=%d graph=%d fuse=%d variant=%d dt=%d : %9.3f us  %8.1f GB/s (algorithmic)  %8.2f TFLOP/s\n", M, K, N, g, sets, use_graph, fuse, variant, dtype, us,
          bytes / us / 1e3, 2.0 * M * K * N / us / 1e6);
   return 0;
 }
