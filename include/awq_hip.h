@@ -167,10 +167,22 @@ int awq_gemm_repacked_ws(const void* x, int64_t ldx, const void* packed, const v
  *                    awq_repacked_sharedx_bf16.hip).  No workspace is used.  Not built: a bf16 form of AWQ_RP_SHARED_X_WIDE (three /
  *                    four row tiles in one launch) gave wrong sums on the MI355X for a reason not found.
  *                    AWQ_RP_SHARED_X and AWQ_RP_SHARED_X_WIDE refuse bf16; this variant refuses fp16.
+ *   AWQ_RP_TILES_BF16  any M >= 1, bf16, group_size % 128 == 0, ldx % 8 == 0, x 16-byte aligned, spans inside 32-bit buffer
+ *                    offsets (ldx < 2^22): the hand-pipelined bf16 MFMA tiles (awq_repacked_prefill_bf16.hip), planned as the
+ *                    automatic route runs them: 128 x 256 tiles for whole rounds of the CUs + 128 x 192 tiles for the remaining
+ *                    columns, or 128 x 128 tiles where that is cheaper.  Every weight is the bf16 awq_dequantize produces (normal
+ *                    scales of magnitude >= 2^-122).  No workspace is used.
+ *   AWQ_RP_TILES_BF16_WIDE  the same kernel and domain: floor(ceil(N / 16) / 16) whole 256-wide column tiles in one launch, the
+ *                    remaining column groups in 192-wide tiles in a second.
+ *   AWQ_RP_TILES_BF16_NARROW  the same kernel and domain: 128 x 128 tiles everywhere, one launch.
+ *                    The three refuse fp16 and group sizes 32 / 64.
  * Returns AWQ_ERR_BAD_VARIANT for an unknown variant or a shape / dtype outside the variant's domain; nothing is launched then.
  * (Enumerators are only ever added: an added variant does not move AWQ_HIP_ABI_VERSION.)
  */
-enum awq_repacked_variant { AWQ_RP_AUTO = 0, AWQ_RP_SHARED_X = 1, AWQ_RP_SHARED_X_WIDE = 2, AWQ_RP_SHARED_X_BF16 = 3 };
+enum awq_repacked_variant {
+  AWQ_RP_AUTO = 0, AWQ_RP_SHARED_X = 1, AWQ_RP_SHARED_X_WIDE = 2, AWQ_RP_SHARED_X_BF16 = 3,
+  AWQ_RP_TILES_BF16 = 4, AWQ_RP_TILES_BF16_WIDE = 5, AWQ_RP_TILES_BF16_NARROW = 6
+};
 
 int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const void* bias, void* y, void* workspace,
                          size_t workspace_bytes, int64_t M, int64_t K, int64_t N, int64_t group_size, int dtype, int variant,

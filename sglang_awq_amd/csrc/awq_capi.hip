@@ -74,6 +74,15 @@ static int repacked_dispatch(const GemmArgs& a, const void* packed) {
     c.y = (char*)a.y + (size_t)16 * a.N * 2;
     return launch_gemv_repacked(c, packed);
   }
+  // bf16, g % 128 == 0, 33 rows and up: the hand-pipelined bf16 tiles in the cells where they measured faster than the generic tiles
+  // (route::tiles_bf16_wins)
+  if (a.dtype == AWQ_DTYPE_BF16 && a.g % 128 == 0) {
+    static const int env_tb = lab_env("AWQ_TILES_BF16", -1);      // lab knob: 0 = never (the previous route), 1 = wherever its domain allows
+    if (env_tb < 0 ? route::tiles_bf16_wins(M, a.K, a.N) : env_tb != 0) {
+      const int rs = launch_gemm_repacked_tiles_bf16(a, packed, 0);
+      if (rs != AWQ_ERR_BAD_VARIANT) return rs;
+    }
+  }
   if (!repacked_fast(a.K, a.N, a.g, a.dtype)) return launch_gemm_repacked_tiled(a, packed);   // bf16 / g in {32, 64}: the generic tiles from 33 rows on
   const bool aligned = a.ldx % 8 == 0 && (((uintptr_t)a.x) & 15) == 0;
   const int64_t wide_tiles = ((M + 127) / 128) * ((a.N + 255) / 256);
@@ -280,7 +289,8 @@ int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const v
                          size_t workspace_bytes, int64_t M, int64_t K, int64_t N, int64_t group_size, int dtype, int variant,
                          void* stream) {
   if (variant == AWQ_RP_AUTO) return awq_gemm_repacked_ws(x, ldx, packed, bias, y, workspace, workspace_bytes, M, K, N, group_size, dtype, stream);
-  if (variant != AWQ_RP_SHARED_X && variant != AWQ_RP_SHARED_X_WIDE && variant != AWQ_RP_SHARED_X_BF16) return AWQ_ERR_BAD_VARIANT;
+  const bool tiles_bf16 = variant == AWQ_RP_TILES_BF16 || variant == AWQ_RP_TILES_BF16_WIDE || variant == AWQ_RP_TILES_BF16_NARROW;
+  if (variant != AWQ_RP_SHARED_X && variant != AWQ_RP_SHARED_X_WIDE && variant != AWQ_RP_SHARED_X_BF16 && !tiles_bf16) return AWQ_ERR_BAD_VARIANT;
   if (!packed) return AWQ_ERR_NULL_POINTER;
   if (K <= 0 || N <= 0 || group_size <= 0 || N % 8 || K % group_size || M < 0 || ldx < K) return AWQ_ERR_BAD_SHAPE;
   if (M == 0) return AWQ_OK;
@@ -293,6 +303,7 @@ int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const v
   a.M = (int)M; a.K = (int)K; a.N = (int)N; a.g = (int)group_size; a.dtype = dtype; a.tune = 0;
   a.stream = (hipStream_t)stream;
   if (variant == AWQ_RP_SHARED_X_BF16) return launch_gemv_repacked_sharedx_bf16(a, packed);
+  if (tiles_bf16) return launch_gemm_repacked_tiles_bf16(a, packed, variant == AWQ_RP_TILES_BF16 ? 0 : variant == AWQ_RP_TILES_BF16_WIDE ? 256 : 128);
   return variant == AWQ_RP_SHARED_X ? launch_gemv_repacked_sharedx(a, packed, false) : launch_gemv_repacked_sharedx_wide(a, packed);
 }
 

@@ -2,7 +2,7 @@
 // Every threshold the launchers use is a named constant here; the launchers (awq_capi.hip: repacked_dispatch; awq_repacked.hip:
 // launch_gemv_repacked; awq_repacked_splitk.hip: rps_plan; awq_repacked_prefill.hip: launch_gemm_repacked_pipelined) only apply them.
 // fp16, group size a multiple of 128 unless noted; g in {32, 64} takes the generic kernels of awq_repacked_ext.hip at every M, and so does
-// bf16 except in the cells of the bf16 row below.
+// bf16 except in the cells of the two bf16 rows below.
 //
 //  rows M        matrix                                   kernel                                        measured (us; source)
 //  ------------  ---------------------------------------  --------------------------------------------  ------------------------------------------------
@@ -26,6 +26,9 @@
 //  bf16 1..64    g % 128 == 0, N <= 32768: 17..32 rows on every   gemv_sharedx_bf16_kernel (the 32-row kernel's   4096 x 22016 at 16 / 32 / 64 rows 20.8 -> 18.7 / 40.8 -> 21.4 / 85.4 -> 41.5;
 //                strip width, 1..16 on 5- and 6-group strips,     structure, dequantisation in fp32; 33..64 rows  4096 x 4096 at 32 rows 13.3 -> 9.5 (kbench_sharedx_bf16_ab.txt)
 //                33..64 on N > 8192 (kSharedXBf16MinRows)         as two launches)
+//  bf16 33..     g % 128 == 0, wherever the bf16 GEMV above is    gemm_repacked_pipelined_bf16_kernel: 128 x 256  4096 x 22016 at 128 / 2048 / 4096 rows 87.5 -> 44.5 / 518 -> 367 / 950 -> 702;
+//                not routed (tiles_bf16_wins)                     + 128 x 192 or 128 x 128 tiles, dequantisation  11008 x 4096 at 64 / 2048 rows 215 -> 105 / 226 -> 172
+//                                                                 by v_fma_mix_f32 from the fp16 magic words      (kbench_tiles_bf16_ab.txt)
 //  33..160       while passes cost less than the tiles     passes of <= 32 rows of the GEMV                a pass 10.3 / 13.2 / 19.7 / 22.8 us on 4096 x 4096 / x 11008 / x 22016 /
 //                (gemv_passes_max: 2..4 passes)                                                           11008 x 4096; under-filled tiles ~1.12 us per k-block: 37-44 / 91 us
 //                                                                                                         (r03_kbench_middle_rows_ab.txt: 4096 x 22016 at 128 rows 78.6 -> 44)
@@ -183,6 +186,36 @@ inline bool sharedx_bf16_wins(int64_t M, int64_t K, int64_t N) {
 constexpr double kNarrowRound192 = 0.84;          // a round of 128 x 192 tiles / a round of 128 x 256 tiles (62 vs 73.5 us at K = 4096)
 constexpr double kNarrowRound128 = 0.65;          // a round of 128 x 128 tiles (43.5 us for 172 tiles at M = 256, 4096 x 11008)
 constexpr double kSecondLaunch = 0.02;
+
+// ---- bf16 hand-pipelined tiles (awq_repacked_prefill_bf16.hip; awq_capi.hip: repacked_dispatch)
+// Round model of its planned form, as above, from full rounds of 16 x 16 tiles at K = 4096 (profiles/kbench_tiles_bf16_ab.txt): 71.5 us
+// for 256-wide tiles (fp16: 73.5), 59.1 for 192-wide, 47.9 for 128-wide (172 of them at 256 rows on 4096 x 11008: 44.4 against 64.0
+// for the 86 wide ones).  The second launch was not measured on its own: the fp16 value.
+constexpr double kTilesBf16Round192 = 0.83;
+constexpr double kTilesBf16Round128 = 0.67;
+constexpr double kTilesBf16SecondLaunch = 0.02;
+// Routed from 33 rows: consulted after sharedx_bf16_wins, so at 33 .. 64 rows only where the two-launch bf16 GEMV is not routed
+// (N <= 8192 or N > 32768).  The forced planned form (variant 4) against the parent route, us old -> new at 33 / 64 / 65 / 96 / 128 /
+// 160 / 256 / 512 / 2048 / 4096 rows, g = 128, every cell measured twice, spread of identical runs at most 0.9 % (median 0.1 %):
+//   4096 x 4096    84.3 -> 41.4 / 84.5 -> 41.5 / 84.5 -> 41.6 / 84.7 -> 41.7 / 84.9 -> 42.0 / 85.2 -> 42.0 / 85.1 -> 42.1 / 86.9 -> 43.0 / 95.7 -> 75.0 / 181.4 -> 141.5
+//   4096 x 12288   (33 / 64 rows: the GEMV stays, 25.3 / 28.8 against 42.6 / 42.8) 85.4 -> 42.8 / 86.1 -> 43.1 / 87.2 -> 43.4 / 87.5 -> 43.9 / 87.5 -> 44.5 /
+//                  89.4 -> 60.7 / 262.8 -> 202.1 / 519.1 -> 391.4
+//   4096 x 22016   (33 / 64 rows: the GEMV stays, 38.6 / 42.5 against 43.0 / 43.3) 85.5 -> 43.4 / 86.2 -> 44.1 / 87.5 -> 44.5 / 88.8 -> 55.3 / 88.9 -> 57.4 /
+//                  172.8 -> 109.3 / 518.2 -> 367.5 / 950.1 -> 701.9
+//   11008 x 4096   214.6 -> 105.1 / 214.9 -> 105.2 / 214.9 -> 105.2 / 217.5 -> 105.3 / 221.4 -> 105.7 / 221.0 -> 105.1 / 221.2 -> 105.0 / 221.3 -> 105.3 /
+//                  225.6 -> 172.1 / 444.3 -> 335.9
+//   8192 x 28672   (33 / 64 rows: the GEMV stays although the tiles measured 84.0 -> 81.1 / 91.2 -> 82.1: one matrix of that strip width) 163.1 -> 82.2 /
+//                  164.3 -> 82.9 / 165.7 -> 84.6 / 167.2 -> 121.1 / 167.6 -> 125.4 / 329.7 -> 235.4 / 1154.1 -> 876.5 / 2334.6 -> 1748.2
+// The parent in every routed cell is gemm_rpx_tiled_kernel, the same decomposition compiler-scheduled, and no measured cell lost, so
+// the rule is rows alone; shapes between and beyond the measured ones (other K, N > 32768) were not measured.  The fp16 routes on the
+// same shapes: 72.1 / 137.0 us at 2048 / 4096 rows on 4096 x 4096, 679.6 at 4096 rows on 4096 x 22016 (bf16: 3 % behind); under-filled
+// launches (one tile per CU or fewer: ~1.3 us per k-block) stay 2 .. 4 x behind fp16's split-K and GEMV-pass routes, which bf16 lacks.
+constexpr int kTilesBf16MinRows = 33;
+// A pure function of the shape: the same call always takes the same route.
+inline bool tiles_bf16_wins(int64_t M, int64_t K, int64_t N) {
+  (void)K; (void)N;
+  return M >= kTilesBf16MinRows;
+}
 
 }  // namespace route
 }  // namespace awq

@@ -89,6 +89,9 @@ int launch_gemv_repacked_sharedx_wide(const GemmArgs& a, const void* packed);
 // bf16, g % 128 == 0: the bf16 form of the 32-row kernel (awq_repacked_sharedx_bf16.hip); 1 .. 32 rows on N <= 32768 in one launch,
 // 33 .. 64 rows on 8192 < N <= 32768 in two; BAD_VARIANT outside
 int launch_gemv_repacked_sharedx_bf16(const GemmArgs& a, const void* packed);
+// bf16, g % 128 == 0, any M >= 1: hand-pipelined MFMA tiles (awq_repacked_prefill_bf16.hip); width 0 = planned (256-wide tiles for whole
+// rounds + 192-wide remainder, or 128 x 128 tiles), 256 = whole 256-wide tiles + 192-wide remainder, 128 = 128 x 128 tiles; BAD_VARIANT outside
+int launch_gemm_repacked_tiles_bf16(const GemmArgs& a, const void* packed, int width);
 int launch_gemv_repacked_fused(const GemmArgs& a, const void* packed);   // norm prologue and / or SiLU-mul epilogue (awq_repacked_fused.hip)
 int launch_gemv_repacked_moe(const GemmArgs& a, const void* packed);     // expert-indirect M = 1 GEMVs, one grid row per (token, expert) slot
 int launch_gemm_repacked_tiled(const GemmArgs& a, const void* packed);   // any M, MFMA-bound prefill shapes

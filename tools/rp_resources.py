@@ -8,7 +8,7 @@ import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRCS = [os.path.join(ROOT, "sglang_awq_amd", "csrc", f) for f in ("awq_repacked.hip", "awq_repacked_fused.hip", "awq_repacked_loop.hip", "awq_repacked_sharedx.hip", "awq_repacked_sharedx_wide.hip", "awq_repacked_sharedx_bf16.hip", "awq_repacked_ext.hip",
-                                                                   "awq_repacked_prefill.hip")]
+                                                                   "awq_repacked_prefill.hip", "awq_repacked_prefill_bf16.hip")]
 
 
 def main():
