@@ -82,7 +82,8 @@ int awq_aux_moe_gemv(const void* x, int64_t ldx, int x_div, const void* packed_e
  * the pairs row_map[16 b .. 16 b + 15] (pair index p -> activation row p / x_div; -1 = padding, nothing is stored for it) with
  * the repacked weight of expert block_expert[b] (< 0: unused block, skipped) and writes output row p of y [pairs, N] (or
  * [pairs, N / 2] with silu_mul); slot_scale[p] as in awq_aux_moe_gemv.  One launch streams each active expert once per 16 of its
- * rows.  fp16, group_size % 128 == 0; AWQ_ERR_BAD_VARIANT otherwise. */
+ * rows.  fp16 or bf16 (dtype; x, the experts' scales and y all of it), group_size % 128 == 0; AWQ_ERR_BAD_VARIANT otherwise.  In bf16
+ * the rounding points are the same with bf16 in place of fp16: silu_mul writes bf16(bf16(silu(bf16 gate)) * bf16 up). */
 /* The alignment step itself on the device, one small launch: ids [pairs] int32 -> row_map [16 num_blocks] (pair indices grouped by
  * expert, each expert's run padded with -1 to a multiple of 16) and block_expert [num_blocks] (-1 = unused block), num_blocks >=
  * ceil(pairs / 16) + num_experts (the static bound).  Ids outside [0, num_experts) are dropped.  The order of the rows inside an expert's run
@@ -99,7 +100,9 @@ int awq_aux_moe_gemv_blocks(const void* x, int64_t ldx, int x_div, const void* p
  * layers/moe/fused_moe_triton/fused_moe.py) — each active expert is streamed once per 128 of its rows instead of once per 16.
  * awq_aux_moe_align_blocks_n: block_rows in {16, 64, 128}; row_map [block_rows * num_blocks], num_blocks >= ceil(pairs / block_rows) +
  * num_experts.  awq_aux_moe_gemm_blocks: same arguments and rounding points as awq_aux_moe_gemv_blocks over blocks of block_rows =
- * 128 or 64 rows (64: layers of many thinly loaded experts — half the MFMA work per streamed weight; silu_mul: N / 16 even). */
+ * 128 or 64 rows (64: layers of many thinly loaded experts — half the MFMA work per streamed weight; silu_mul: N / 16 even).  fp16 or
+ * bf16, group_size % 128 == 0; bf16 runs 128-row blocks only (block_rows = 64 with bf16: AWQ_ERR_BAD_VARIANT).  AWQ_ERR_BAD_VARIANT
+ * also where an activation row would start 2 GiB or more behind x (callers run the 16-row blocks instead). */
 int awq_aux_moe_align_blocks_n(const int32_t* ids, int64_t pairs, int64_t num_experts, int block_rows, int32_t* row_map,
                                int32_t* block_expert, int64_t num_blocks, void* stream);
 int awq_aux_moe_gemm_blocks(const void* x, int64_t ldx, int x_div, const void* packed_experts, int64_t expert_stride_bytes,

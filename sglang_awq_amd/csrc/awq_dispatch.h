@@ -42,6 +42,10 @@
 //  the torch op  M >= 33 without a cached copy             awq_repack into the workspace, then the above   11008 x 4096: M = 64 212 -> 63, M = 256 217 -> 118
 //  AWQ-MoE       <= 12 (token, expert) pairs               gemv_rp2_kernel, one grid row per pair          ~17 per pair (E = 8, 4096 / 14336); blocks ~215: cross at ~13
 //                more                                      gemv_rp3_kernel on expert-sorted 16-row blocks  (r03_time_moe.txt; threshold in sglang_awq_amd/moe.py)
+//  AWQ-MoE bf16  below 32 rows per expert on average       gemv_sharedx_bf16_kernel<G, 1, NT, EPI, ROWMAP>  8 / 64 pairs 222 / 223 (fp16 203 / 211; E = 8, 4096 / 14336); E = 256, 7168 / 2048 at
+//                (no slot route)                            on 16-row blocks, strips of 8 / 6 / 4 / 2 groups 2048 pairs 1729 (fp16 1587) (time_moe_bf16.txt)
+//  AWQ-MoE bf16  from 32 rows per expert                   gemm_repacked_pipelined_bf16_kernel<4, MOE, EPI>  4096 tokens 3405 (fp16 3259) Mixtral-like; blocks / tiles 554 / 552 at 32 rows per
+//                (no 64-row tiles)                          on 128-row blocks                                expert, 613 / 556 at 40; DeepSeek-V3-like 4057 / 3604 at 32 (time_moe_bf16.txt)
 #pragma once
 
 #include <stddef.h>

@@ -104,6 +104,12 @@ size_t pf_split_workspace_bytes(int64_t M, int64_t K, int64_t N);
 // the same kernel over expert-sorted 128-row blocks of (token, expert) pairs (AWQ-MoE prefill; awq_aux_moe_gemm_blocks)
 int launch_gemm_repacked_moe_tiles(const GemmArgs& a, const void* packed_experts, const int* row_map, const int* block_expert, int num_blocks,
                                    int block_rows, const float* slot_scale, long long expert_stride, int x_div, bool silu_mul);
+// bf16, g % 128 == 0: the AWQ-MoE forms of the two bf16 kernels — expert-sorted 16-row blocks on gemv_sharedx_bf16_kernel
+// (awq_repacked_sharedx_bf16.hip) and 128-row blocks on gemm_repacked_pipelined_bf16_kernel (awq_repacked_prefill_bf16.hip); a.M is ignored
+int launch_gemv_repacked_sharedx_bf16_moe(const GemmArgs& a, const void* packed_experts, const int* row_map, const int* block_expert,
+                                          int num_blocks, const float* slot_scale, long long expert_stride, int x_div, bool silu_mul);
+int launch_gemm_repacked_moe_tiles_bf16(const GemmArgs& a, const void* packed_experts, const int* row_map, const int* block_expert,
+                                        int num_blocks, const float* slot_scale, long long expert_stride, int x_div, bool silu_mul);
 
 // Opt a kernel in to more than 64 KiB of dynamic LDS on the CURRENT device.  The attribute belongs to the function object of
 // a device, and the shim serves several devices from one process: remember per (kernel, device) instead of once per process.

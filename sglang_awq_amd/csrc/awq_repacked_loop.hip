@@ -405,8 +405,15 @@ extern "C" int awq_aux_moe_gemm_blocks(const void* x, int64_t ldx, int x_div, co
     return AWQ_ERR_BAD_SHAPE;
   if ((((uintptr_t)packed_experts) & 15) || (((uintptr_t)x) & 15) || (((uintptr_t)y) & 1) || (expert_stride_bytes & 15) || ldx % 8)
     return AWQ_ERR_MISALIGNED;
-  if (!repacked_fast(K, N, group_size, dtype) || (silu_mul && N % 32)) return AWQ_ERR_BAD_VARIANT;
-  if ((num_blocks * block_rows / x_div + 1) * ldx >= (int64_t(1) << 31)) return AWQ_ERR_BAD_VARIANT;     // 32-bit activation row offsets in the kernel
+  const bool bf16 = dtype == AWQ_DTYPE_BF16 && group_size % 128 == 0 && repacked_supported(K, N, group_size, dtype);
+  if ((!bf16 && !repacked_fast(K, N, group_size, dtype)) || (silu_mul && N % 32)) return AWQ_ERR_BAD_VARIANT;
+  if (bf16) {
+    if (block_rows != 128) return AWQ_ERR_BAD_VARIANT;               // 64-row bf16 tiles would need a slot table of their own
+    // the kernel's activation offsets are 32-bit BYTE offsets from x: the furthest row read must start below 2 GiB
+    if ((num_blocks * 128 / x_div + 1) * ldx * 2 >= (int64_t(1) << 31)) return AWQ_ERR_BAD_VARIANT;
+  } else if ((num_blocks * block_rows / x_div + 1) * ldx >= (int64_t(1) << 31)) {
+    return AWQ_ERR_BAD_VARIANT;                                        // 32-bit activation row offsets in the kernel
+  }
   const int64_t tiles = num_blocks * ((rp_groups(N) + 15) / 16);
   if (tiles >= (int64_t(1) << 31)) return AWQ_ERR_BAD_VARIANT;
   GemmArgs a;
@@ -414,6 +421,9 @@ extern "C" int awq_aux_moe_gemm_blocks(const void* x, int64_t ldx, int x_div, co
   a.workspace = nullptr; a.workspace_bytes = 0;
   a.M = (int)(num_blocks * block_rows); a.K = (int)K; a.N = (int)N; a.g = (int)group_size; a.dtype = dtype; a.tune = 0;
   a.stream = (hipStream_t)stream;
+  if (bf16)
+    return launch_gemm_repacked_moe_tiles_bf16(a, packed_experts, row_map, block_expert, (int)num_blocks, slot_scale, (long long)expert_stride_bytes,
+                                               x_div, silu_mul != 0);
   return launch_gemm_repacked_moe_tiles(a, packed_experts, row_map, block_expert, (int)num_blocks, block_rows, slot_scale,
                                         (long long)expert_stride_bytes, x_div, silu_mul != 0);
 }
@@ -428,12 +438,17 @@ extern "C" int awq_aux_moe_gemv_blocks(const void* x, int64_t ldx, int x_div, co
     return AWQ_ERR_BAD_SHAPE;
   if ((((uintptr_t)packed_experts) & 15) || (((uintptr_t)x) & 15) || (((uintptr_t)y) & 1) || (expert_stride_bytes & 15) || ldx % 8)
     return AWQ_ERR_MISALIGNED;
-  if (!repacked_fast(K, N, group_size, dtype) || K / 128 >= 4096 || group_size / 128 >= 4096 || (silu_mul && N % 32)) return AWQ_ERR_BAD_VARIANT;
+  const bool bf16 = dtype == AWQ_DTYPE_BF16 && group_size % 128 == 0 && repacked_supported(K, N, group_size, dtype);
+  if ((!bf16 && !repacked_fast(K, N, group_size, dtype)) || K / 128 >= 4096 || group_size / 128 >= 4096 || (silu_mul && N % 32))
+    return AWQ_ERR_BAD_VARIANT;
   GemmArgs a;
   a.x = x; a.ldx = ldx; a.qweight = nullptr; a.scales = nullptr; a.qzeros = nullptr; a.bias = nullptr; a.y = y;
   a.workspace = nullptr; a.workspace_bytes = 0;
   a.M = 16; a.K = (int)K; a.N = (int)N; a.g = (int)group_size; a.dtype = dtype; a.tune = 0;
   a.stream = (hipStream_t)stream;
+  if (bf16)
+    return launch_gemv_repacked_sharedx_bf16_moe(a, packed_experts, row_map, block_expert, (int)num_blocks, slot_scale, (long long)expert_stride_bytes,
+                                                 x_div, silu_mul != 0);
   const int NG = rp_groups(N);
   // Strip width.  A launch holds several 16-row blocks (one per active expert at least), so strips need not be one-per-CU narrow; every
   // workgroup stages all 16 activation rows, so wider strips mean less activation traffic.  6 column groups: a stage of 6 units is a

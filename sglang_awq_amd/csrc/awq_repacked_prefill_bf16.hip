@@ -37,6 +37,11 @@
 // of every j = 1 fragment; the 8 LDS writes of the next x tile behind every fourth MFMA of (1, 2) (1, 3) (2, 0) (2, 1) (NJ = 3: MFMAs
 // 0, 3, 6 of (1, 2) (2, 0) (2, 2); NJ = 2: every second MFMA of (1, 0) (2, 0)); the request for the tile after it behind them; the
 // barrier behind the first MFMA of (3, 0).
+//
+// AWQ-MoE form (template parameters MOE, EPI at NJ = 4; awq_aux_moe_gemm_blocks with bf16): 128-row blocks of expert-sorted (token,
+// expert) pairs, the expert chosen per row tile, x rows gathered and output rows scattered through row_map — see PfbMoe below.  Only the
+// tile order, the x offsets and the epilogue differ from the dense form (198 / 199 VGPRs + 128 AGPRs, zero scratch, as the dense 199).
+// 64-row tiles (MI = 4) would need a slot table of their own (17 ops behind 4 MFMAs) and are not built.
 #include <cstdlib>
 
 #include "awq_prefill_common.h"
@@ -113,14 +118,31 @@ constexpr int kPfbRowBlock = 4;       // row tiles per super-row of the tile ord
 
 // NJ = column groups (16 columns) per wave: 4 -> 128 x 256 tiles, 3 -> 128 x 192, 2 -> 128 x 128.  A launch covers the column groups
 // [cg_base, cg_base + ng_region) of the matrix (the host cuts N into regions: launch_gemm_repacked_tiles_bf16).
-template <int NJ>
+//
+// MOE (AWQ-MoE prefill, NJ = 4; awq_aux_moe_gemm_blocks with bf16): the rows are (token, expert) pairs grouped by expert into 128-row
+// blocks (awq_aux_moe_align_blocks_n); row tile t takes its weights from expert block_expert[t] (expert_stride bytes apart; < 0: unused
+// tile, the workgroup leaves before any barrier), its row r reads activation row row_map[128 t + r] / x_div and writes output row
+// row_map[128 t + r] (-1 = padding: reads row 0, stores nothing), the fp32 sums multiplied by slot_scale[pair] before the one rounding.
+// Plain tile order (the row tiles of a super-row would belong to different experts).  EPI = 1: the column groups alternate gate / up
+// and act = bf16(bf16(silu(bf16 gate)) * bf16 up) is written, N / 2 wide.  The slot table and the main loop are those of the dense form.
+struct PfbMoe {
+  const int* row_map;
+  const int* block_expert;
+  const float* slot_scale;
+  long long expert_stride;
+  int x_div;
+};
+
+template <int NJ, bool MOE = false, int EPI = 0>
 __global__ __launch_bounds__(kPfbThreads, 1) void gemm_repacked_pipelined_bf16_kernel(const uint16_t* __restrict__ x, int64_t ldx,
                                                                                        const u32x4_t* __restrict__ qw_r,
                                                                                        const uint32_t* __restrict__ zs_r,
                                                                                        const void* __restrict__ bias, void* __restrict__ y,
                                                                                        int M, int K, int N, int g, int NG, int nbx, int nby,
-                                                                                       int cg_base, int ng_region) {
+                                                                                       int cg_base, int ng_region, PfbMoe moe) {
   static_assert(NJ >= 2 && NJ <= 4, "128 x 128 .. 128 x 256 tiles");
+  static_assert(!MOE || NJ == 4, "expert blocks run 128 x 256 tiles");
+  static_assert(!EPI || MOE, "SiLU-mul epilogue: whole (gate, up) pairs per wave, MoE form only");
   extern __shared__ __attribute__((aligned(16))) unsigned char As[];      // 2 x 32 KiB
   constexpr int MI = 8, BM = kPfBM, AL = 8;           // row tiles per wave; rows per workgroup tile; x-tile chunks (16 B) per thread
   const int tid = threadIdx.x, lane = tid & 63;
@@ -134,9 +156,17 @@ __global__ __launch_bounds__(kPfbThreads, 1) void gemm_repacked_pipelined_bf16_k
   // the 32 tiles an XCD runs together cover 4 row tiles x 8 column tiles: x and weights each shared in its L2 (see the fp16 kernel)
   const int sb_tiles = kPfbRowBlock * nbx, sb = logical / sb_tiles, in_sb = logical - sb * sb_tiles;
   const int rows_sb = nby - sb * kPfbRowBlock < kPfbRowBlock ? nby - sb * kPfbRowBlock : kPfbRowBlock;
-  const int bm = (sb * kPfbRowBlock + in_sb % rows_sb) * BM;
-  const int cg_tile = cg_base + (in_sb / rows_sb) * (4 * NJ) + wn * NJ;       // this wave's first column group
+  int bm = (sb * kPfbRowBlock + in_sb % rows_sb) * BM;
+  int cg_tile = cg_base + (in_sb / rows_sb) * (4 * NJ) + wn * NJ;             // this wave's first column group
   const int cg_end = cg_base + ng_region < NG ? cg_base + ng_region : NG;
+  if constexpr (MOE) {
+    bm = (logical / nbx) * BM;                          // plain order: the column tiles of an expert's row tile together
+    cg_tile = cg_base + (logical % nbx) * (4 * NJ) + wn * NJ;
+    const int eid = moe.block_expert[bm / BM];          // uniform over the workgroup, read before any barrier
+    if (eid < 0) return;
+    qw_r = (const u32x4_t*)((const unsigned char*)qw_r + (long long)eid * moe.expert_stride);
+    zs_r = (const uint32_t*)((const unsigned char*)zs_r + (long long)eid * moe.expert_stride);
+  }
 
   __amdgpu_buffer_rsrc_t rw[NJ];                       // this wave's column groups: [KB][64 lanes] dwordx4
   uint32_t zoff_s[NJ];                                 // byte offset of the group's first scale word in zs_r
@@ -148,7 +178,7 @@ __global__ __launch_bounds__(kPfbThreads, 1) void gemm_repacked_pipelined_bf16_k
     zoff_s[j] = (uint32_t)cgj * (uint32_t)groups * 64u;
   }
   const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void*)zs_r, 0, 0x7fffffff, kPfRsrcFlags);
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)bm * ldx), 0, 0x7fffffff, kPfRsrcFlags);
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (MOE ? (size_t)0 : (size_t)bm * ldx)), 0, 0x7fffffff, kPfRsrcFlags);
   const int lane16 = lane * 16, r4 = r * 4;
 
   u32x4_t a_st[AL];
@@ -162,7 +192,11 @@ __global__ __launch_bounds__(kPfbThreads, 1) void gemm_repacked_pipelined_bf16_k
   for (int i = 0; i < AL; ++i) {
     const int c = tid + kPfbThreads * i;
     const int row = c >> 4, chunk = c & 15;
-    const int mr = bm + row < M ? row : M - 1 - bm;
+    int mr = bm + row < M ? row : M - 1 - bm;
+    if constexpr (MOE) {                               // byte offsets from x itself (below 2 GiB: the host's guard)
+      const int pr = moe.row_map[bm + row];
+      mr = pr >= 0 ? pr / moe.x_div : 0;
+    }
     xoff[i] = (uint32_t)((size_t)mr * ldx + chunk * 8) * 2u;
   }
   auto load_a = [&](int kb) {
@@ -268,6 +302,49 @@ __global__ __launch_bounds__(kPfbThreads, 1) void gemm_repacked_pipelined_bf16_k
 
   // the output tile: rounded (and biased, second rounding) exactly as store_output<bf16> does, parked wave-privately in the idle x
   // buffers 64 rows at a time, stored as 16 bytes per lane (8 lanes per 128-byte row run of a 64-column wave)
+  if constexpr (MOE) {
+    // the same route with the routed weight on the fp32 sums and, EPI = 1, SiLU-mul over the wave's (gate, up) pairs of groups at the
+    // rounding points of the bf16 GEMV's epilogue; every lane then stores 16 bytes of its pair's output row (rows scatter by pair index)
+    constexpr int WO = EPI == 1 ? NJ * 8 : NJ * 16;                            // output columns of this wave
+    const int width = EPI == 1 ? N / 2 : N;
+    const int n_wave = EPI == 1 ? (cg_tile >> 1) * 16 : cg_tile * 16;          // first output column of this wave
+    __syncthreads();
+    uint16_t* const tw = (uint16_t*)As + (size_t)wn * (64 * WO);
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int rl = mi * 16 + 4 * q + i;
+          const int pr = moe.row_map[bm + half * 64 + rl];
+          const float sc = (pr >= 0 && moe.slot_scale) ? moe.slot_scale[pr] : 1.f;
+          if constexpr (EPI == 1) {
+#pragma unroll
+            for (int j = 0; j < NJ; j += 2) {
+              const float xg = round_to_dtype<AWQ_DTYPE_BF16>(acc[half * 4 + mi][j][i] * sc);
+              const float up = round_to_dtype<AWQ_DTYPE_BF16>(acc[half * 4 + mi][j + 1][i] * sc);
+              tw[rl * WO + (j >> 1) * 16 + r] = float_to_bf16_bits(round_to_dtype<AWQ_DTYPE_BF16>(xg / (1.f + __expf(-xg))) * up);
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) tw[rl * WO + j * 16 + r] = float_to_bf16_bits(acc[half * 4 + mi][j][i] * sc);
+          }
+        }
+      // (a wave's LDS accesses complete in order: no barrier between its own writes and reads)
+#pragma unroll
+      for (int p = 0; p < WO / 8; ++p) {
+        const int f = (p * 64 + lane) * 8;
+        const int row = f / WO, col = f - row * WO;
+        const int pr = moe.row_map[bm + half * 64 + row];
+        const int n = n_wave + col;
+        // (a 16-column output group is complete or absent: cg_end and N / width are multiples of what a group covers; width % 8 == 0)
+        const bool in = EPI == 1 ? (cg_tile + 2 * (col >> 4) + 1 < cg_end) : (cg_tile + (col >> 4) < cg_end);
+        if (pr >= 0 && in && n < width) *(u32x4_t*)((uint16_t*)y + (size_t)pr * width + n) = *(const u32x4_t*)(tw + f);
+      }
+    }
+    return;
+  }
   constexpr int WC = NJ * 16;
   __syncthreads();                                     // every wave has read its last x fragments: the buffers are free
   uint16_t* const tw = (uint16_t*)As + (size_t)wn * (64 * WC);
@@ -309,8 +386,34 @@ static int pfb_launch_region(const GemmArgs& a, const u32x4_t* qw_r, const uint3
   static unsigned long long opted[2] = {0ull, 0ull};
   if (!opt_in_dynamic_lds((const void*)gemm_repacked_pipelined_bf16_kernel<NJ>, (int)lds, opted)) return AWQ_ERR_LAUNCH;
   hipLaunchKernelGGL((gemm_repacked_pipelined_bf16_kernel<NJ>), dim3(nbx * nby), dim3(kPfbThreads), lds, a.stream, (const uint16_t*)a.x, a.ldx,
-                     qw_r, zs_r, a.bias, a.y, a.M, a.K, a.N, a.g, NG, nbx, nby, cg_base, ng_region);
+                     qw_r, zs_r, a.bias, a.y, a.M, a.K, a.N, a.g, NG, nbx, nby, cg_base, ng_region, PfbMoe{nullptr, nullptr, nullptr, 0ll, 1});
   return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
+}
+
+// AWQ-MoE over expert-sorted 128-row blocks: `num_blocks` row tiles x ceil(NG / 16) column tiles of 256 (the remainder tile is clamped)
+template <int EPI>
+static int pfb_launch_moe(const GemmArgs& a, const u32x4_t* qw_r, const uint32_t* zs_r, int NG, int num_blocks, const PfbMoe& moe) {
+  const int nbx = (NG + 15) / 16, nby = num_blocks;
+  const size_t lds = 2 * kPfBM * 256;
+  static unsigned long long opted[2] = {0ull, 0ull};
+  if (!opt_in_dynamic_lds((const void*)gemm_repacked_pipelined_bf16_kernel<4, true, EPI>, (int)lds, opted)) return AWQ_ERR_LAUNCH;
+  hipLaunchKernelGGL((gemm_repacked_pipelined_bf16_kernel<4, true, EPI>), dim3(nbx * nby), dim3(kPfbThreads), lds, a.stream, (const uint16_t*)a.x,
+                     a.ldx, qw_r, zs_r, nullptr, a.y, num_blocks * kPfBM, a.K, a.N, a.g, NG, nbx, nby, 0, NG, moe);
+  return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
+}
+
+// The caller (awq_aux_moe_gemm_blocks) has checked that every activation row read starts below 2 GiB from a.x and that the grid fits.
+int launch_gemm_repacked_moe_tiles_bf16(const GemmArgs& a, const void* packed_experts, const int* row_map, const int* block_expert,
+                                        int num_blocks, const float* slot_scale, long long expert_stride, int x_div, bool silu_mul) {
+  if (a.dtype != AWQ_DTYPE_BF16 || a.g % 128 || !repacked_supported(a.K, a.N, a.g, a.dtype) || a.ldx < a.K || a.ldx % 8 ||
+      (((uintptr_t)a.x) & 15) || !pipelined_addressable(a) || num_blocks < 1 || x_div < 1)
+    return AWQ_ERR_BAD_VARIANT;
+  const int NG = rp_groups(a.N);
+  if (silu_mul && (a.N % 32 || (NG & 1))) return AWQ_ERR_BAD_VARIANT;
+  const u32x4_t* qw_r = (const u32x4_t*)packed_experts;
+  const uint32_t* zs_r = (const uint32_t*)packed_experts + (size_t)NG * (a.K / 128) * 256;
+  const PfbMoe moe = {row_map, block_expert, slot_scale, expert_stride, x_div};
+  return silu_mul ? pfb_launch_moe<1>(a, qw_r, zs_r, NG, num_blocks, moe) : pfb_launch_moe<0>(a, qw_r, zs_r, NG, num_blocks, moe);
 }
 
 // width 0: the planned form — N cut into a region of 256-wide tiles that fills whole rounds of the 256 CUs and a remainder of 192-wide

@@ -10,8 +10,12 @@
 // r ^ (4 d + q) bank swizzle; x loads issued two chunk bodies ahead (two register sets); one barrier per chunk, all trip counts
 // functions of K alone; the weight ring re-issued the moment a unit has arrived, before it is dequantised; rows >= M and k-blocks past
 // K written as zeros without touching memory (ldx > K is fine); the fixed-order reduction through LDS over the x buffers;
-// store_output<bf16>: one rounding of the fp32 sum, then the bias with a second rounding.  No SiLU-mul epilogue, no folded norm, no
-// MoE form (fp16 only).
+// store_output<bf16>: one rounding of the fp32 sum, then the bias with a second rounding.  No folded norm (fp16 only).
+//
+// AWQ-MoE form (template parameters EPI, ROWMAP; one row tile; awq_aux_moe_gemv_blocks with bf16): a second grid dimension of
+// expert-sorted 16-row blocks, the loader and the final reduction indirected through row_map, the routed weight on the fp32 sums,
+// and the SiLU-mul epilogue over (gate, up) pairs of column groups — see SxbMoe below.  The chunk loop is the dense one: same LDS
+// (sxb_lds(G, 1)), same barriers; the dense instantiations compile to the same registers as before it existed.
 //
 // Dequantisation.  Every W element is the bf16 awq_dequantize produces: (q - z) exact, times the scale as an exact fp32 product,
 // one round-to-nearest-even to bf16 (the statement of it: rpx_dequant<AWQ_DTYPE_BF16>, awq_repacked_ext.hip).  The generic form
@@ -116,13 +120,28 @@ constexpr size_t sxb_lds(int G, int MT) {
   return x2 > red ? x2 : red;
 }
 
-template <int G, int MT, bool NT>
+// ROWMAP (AWQ-MoE, one row tile): grid row b serves the (token, expert) pairs row_map[16 b .. 16 b + 15] (sorted by expert, -1 =
+// padding) with the weights of expert block_expert[b] (< 0: unused block, the workgroup leaves before any barrier); row i of the block
+// is activation row row_map[16 b + i] / x_div (padding: zeros, no load) and output row row_map[16 b + i] (padding: no store), the fp32
+// sums multiplied by slot_scale[pair] before their one rounding.  EPI = 1 (ROWMAP only, G even so that every strip starts on a gate
+// group): the column groups alternate gate / up and act = bf16(bf16(silu(bf16 gate)) * bf16 up) is written, N / 2 wide.
+struct SxbMoe {
+  const int* row_map;
+  const int* block_expert;
+  const float* slot_scale;
+  long long expert_stride;
+  int x_div;
+};
+
+template <int G, int MT, bool NT, int EPI = 0, bool ROWMAP = false>
 __global__ __launch_bounds__(sxb_slots(G) * G * 64) void gemv_sharedx_bf16_kernel(const uint16_t* __restrict__ x, int64_t ldx,
                                                                                  const u32x4_t* __restrict__ qw_r,
                                                                                  const uint32_t* __restrict__ zs_r,
                                                                                  const void* __restrict__ bias, void* __restrict__ y,
                                                                                  int M, int K, int N, int groups, int gmul, int gshift,
-                                                                                 int NG) {
+                                                                                 int NG, SxbMoe moe) {
+  static_assert(!ROWMAP || MT == 1, "an expert block is one row tile");
+  static_assert(!EPI || (ROWMAP && G % 2 == 0), "SiLU-mul: whole (gate, up) pairs of column groups per strip");
   constexpr int S = sxb_slots(G), U = sxb_units(G), C = S * U, NW = S * G, NTH = NW * 64;
   constexpr int ROWS = MT * 16, PIECES = ROWS * C * 16, PL = (PIECES + NTH - 1) / NTH;
   constexpr int BUF = ROWS * C * 256;                      // bytes of one x buffer
@@ -134,6 +153,22 @@ __global__ __launch_bounds__(sxb_slots(G) * G * 64) void gemv_sharedx_bf16_kerne
   int cg0 = blockIdx.x * G;
   if (cg0 + G > NG) cg0 = NG - G;                          // last strip overlaps its neighbour (same values written twice)
   const int c = wave % G, slot = wave / G;                 // this wave's column group and k-block slot
+  const int* rows = nullptr;
+  int xrow[PL];                                            // ROWMAP: activation row of this thread's piece i (-1: padding)
+  if constexpr (ROWMAP) {
+    const int eid = moe.block_expert[blockIdx.y];
+    if (eid < 0) return;                                   // unused block (uniform over the workgroup)
+    qw_r = (const u32x4_t*)((const unsigned char*)qw_r + (long long)eid * moe.expert_stride);
+    zs_r = (const uint32_t*)((const unsigned char*)zs_r + (long long)eid * moe.expert_stride);
+    rows = moe.row_map + (size_t)blockIdx.y * 16;
+    M = 16;
+#pragma unroll
+    for (int i = 0; i < PL; ++i) {
+      const int id = i * NTH + tid;
+      const int p = id < PIECES ? rows[id / (C * 16)] : -1;
+      xrow[i] = p >= 0 ? p / moe.x_div : -1;
+    }
+  }
   const u32x4_t* const wbase = qw_r + (size_t)(cg0 + c) * KB * 64 + lane;
   const uint32_t* const zbase = zs_r + (size_t)(cg0 + c) * groups * 16 + r;
 
@@ -143,9 +178,13 @@ __global__ __launch_bounds__(sxb_slots(G) * G * 64) void gemv_sharedx_bf16_kerne
     for (int i = 0; i < PL; ++i) {
       const int id = i * NTH + tid;
       const int row = id / (C * 16), kk = id - row * (C * 16);
-      const bool in = id < PIECES && row < M && ch * C + (kk >> 4) < KB;
       xv[i] = (u32x4_t){0u, 0u, 0u, 0u};
-      if (in) xv[i] = *(const u32x4_t*)(x + (size_t)row * ldx + (size_t)ch * (C * 128) + kk * 8);
+      if constexpr (ROWMAP) {
+        if (xrow[i] >= 0 && ch * C + (kk >> 4) < KB) xv[i] = *(const u32x4_t*)(x + (size_t)xrow[i] * ldx + (size_t)ch * (C * 128) + kk * 8);
+      } else {
+        const bool in = id < PIECES && row < M && ch * C + (kk >> 4) < KB;
+        if (in) xv[i] = *(const u32x4_t*)(x + (size_t)row * ldx + (size_t)ch * (C * 128) + kk * 8);
+      }
     }
   };
   auto x_park = [&](int b, const u32x4_t (&xv)[PL]) {
@@ -225,21 +264,50 @@ __global__ __launch_bounds__(sxb_slots(G) * G * 64) void gemv_sharedx_bf16_kerne
   __syncthreads();
   const float* const red = (const float*)smem;
   const int SW = 16 * G;
-  for (int idx = tid; idx < M * SW; idx += NTH) {
-    const int m = idx / SW, col = idx - m * SW;
-    const int n = cg0 * 16 + col;
-    if (n >= N) continue;
-    const int cc = col >> 4, e = (((m >> 4) * 64) + ((m & 15) >> 2) * 16 + (col & 15)) * 4 + (m & 3);
-    float v = red[(size_t)cc * MT * 256 + e];
+  if constexpr (EPI == 1) {
+    // strip = G / 2 (gate, up) pairs of column groups (cg0 is even: G and NG are); output column 16 (pair index) + r of act[pairs, N / 2].
+    // Rounding points of the fp16 epilogue (gemv_rp3_kernel) in bf16: gate and up each rounded, silu in fp32 on the rounded gate and
+    // rounded, the product rounded.
+    const int SH = 8 * G, I = N / 2;
+    for (int idx = tid; idx < 16 * SH; idx += NTH) {
+      const int m = idx / SH, col = idx - m * SH;
+      const int pair = col >> 4, r16 = col & 15;
+      const int n = (cg0 / 2 + pair) * 16 + r16;
+      const int orow = rows[m];
+      if (n >= I || orow < 0) continue;
+      const int e = (((m & 15) >> 2) * 16 + r16) * 4 + (m & 3);
+      float gv = red[(size_t)(2 * pair) * 256 + e], uv = red[(size_t)(2 * pair + 1) * 256 + e];
 #pragma unroll
-    for (int s = 1; s < S; ++s) v += red[(size_t)(s * G + cc) * MT * 256 + e];
-    store_output<AWQ_DTYPE_BF16>(y, (size_t)m * N + n, v, bias, n);
+      for (int s = 1; s < S; ++s) {
+        gv += red[(size_t)(s * G + 2 * pair) * 256 + e];
+        uv += red[(size_t)(s * G + 2 * pair + 1) * 256 + e];
+      }
+      if (moe.slot_scale != nullptr) { const float sc = moe.slot_scale[orow]; gv *= sc; uv *= sc; }
+      const float xg = round_to_dtype<AWQ_DTYPE_BF16>(gv);
+      const float act = round_to_dtype<AWQ_DTYPE_BF16>(xg / (1.f + __expf(-xg))) * round_to_dtype<AWQ_DTYPE_BF16>(uv);
+      ((uint16_t*)y)[(size_t)orow * I + n] = float_to_bf16_bits(act);
+    }
+  } else {
+    for (int idx = tid; idx < M * SW; idx += NTH) {
+      const int m = idx / SW, col = idx - m * SW;
+      const int n = cg0 * 16 + col;
+      if (n >= N) continue;
+      int orow = m;
+      if constexpr (ROWMAP) { orow = rows[m]; if (orow < 0) continue; }
+      const int cc = col >> 4, e = (((m >> 4) * 64) + ((m & 15) >> 2) * 16 + (col & 15)) * 4 + (m & 3);
+      float v = red[(size_t)cc * MT * 256 + e];
+#pragma unroll
+      for (int s = 1; s < S; ++s) v += red[(size_t)(s * G + cc) * MT * 256 + e];
+      if constexpr (ROWMAP) { if (moe.slot_scale != nullptr) v *= moe.slot_scale[orow]; }
+      store_output<AWQ_DTYPE_BF16>(y, (size_t)orow * N + n, v, bias, n);
+    }
   }
 }
 
 // ------------------------------------------------------------------------------------------------ host
 // Every instantiation (G = 1 .. 8, one or two row tiles, either load policy) has zero scratch: 62 .. 162 VGPRs, 72 .. 120 of the 128
-// where the workgroup has 16 waves (tools/rp_resources.py).
+// where the workgroup has 16 waves (tools/rp_resources.py).  The AWQ-MoE instantiations (G = 1, 2, 3, 4, 6, 8; SiLU-mul on the even
+// ones) take 0 .. 6 registers more than their dense width (66 .. 100 VGPRs), zero scratch too.
 //
 // 33 .. 64 rows (8192 < N <= 32768 only) run as two launches of this kernel: rows 0 .. 31 on two row tiles, then the rest.  The
 // bf16 form of gemv_sharedx_wide_kernel (three / four row tiles per dequantised fragment, a wave owning two column groups) was
@@ -264,7 +332,22 @@ static int sxb_go(const GemmArgs& a, const SxbLaunch& l) {
     if (!opt_in_dynamic_lds((const void*)kern, kRpMaxLds, opted)) return AWQ_ERR_LAUNCH;
   }
   hipLaunchKernelGGL(kern, dim3(l.nwg), dim3(sxb_slots(G) * G * 64), lds, a.stream, (const uint16_t*)a.x, a.ldx, l.qw_r, l.zs_r, a.bias, a.y,
-                     a.M, a.K, a.N, a.K / a.g, l.gmul, l.gshift, l.NG);
+                     a.M, a.K, a.N, a.K / a.g, l.gmul, l.gshift, l.NG, SxbMoe{nullptr, nullptr, nullptr, 0ll, 1});
+  return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
+}
+
+// the AWQ-MoE form: (strips, blocks) workgroups of one row tile
+template <int G, int EPI>
+static int sxb_go_moe(const GemmArgs& a, const SxbLaunch& l, int num_blocks, const SxbMoe& moe, bool nt) {
+  constexpr size_t lds = sxb_lds(G, 1);
+  static_assert(lds <= 64 * 1024, "no opt-in needed at one row tile");
+  const dim3 grid(l.nwg, num_blocks), block(sxb_slots(G) * G * 64);
+  if (nt)
+    hipLaunchKernelGGL((gemv_sharedx_bf16_kernel<G, 1, true, EPI, true>), grid, block, lds, a.stream, (const uint16_t*)a.x, a.ldx, l.qw_r, l.zs_r,
+                       nullptr, a.y, 16, a.K, a.N, a.K / a.g, l.gmul, l.gshift, l.NG, moe);
+  else
+    hipLaunchKernelGGL((gemv_sharedx_bf16_kernel<G, 1, false, EPI, true>), grid, block, lds, a.stream, (const uint16_t*)a.x, a.ldx, l.qw_r, l.zs_r,
+                       nullptr, a.y, 16, a.K, a.N, a.K / a.g, l.gmul, l.gshift, l.NG, moe);
   return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
 
@@ -318,6 +401,50 @@ int launch_gemv_repacked_sharedx_bf16(const GemmArgs& a, const void* packed) {
     case 7: return sxb_go_g<7>(a, l, nt);
     case 8: return sxb_go_g<8>(a, l, nt);
     default: return AWQ_ERR_BAD_VARIANT;
+  }
+}
+
+// AWQ-MoE over expert-sorted 16-row blocks (awq_aux_moe_gemv_blocks, bf16).  Strip width: a launch holds many blocks (one per active
+// expert at least) and every workgroup stages all 16 rows of its block, so — the fp16 launcher's reasoning — the widest strip the
+// matrix has, not one strip per CU: 8 column groups (16 waves, 32 KiB of x buffers), else 6 / 4 / 2; an odd 3 or 1 only without
+// SiLU-mul, whose strips must start on a gate group.  All of these have zero scratch (tools/rp_resources.py).  Activation rows are
+// addressed with 64-bit offsets: no limit on num_blocks x ldx here.
+int launch_gemv_repacked_sharedx_bf16_moe(const GemmArgs& a, const void* packed_experts, const int* row_map, const int* block_expert,
+                                          int num_blocks, const float* slot_scale, long long expert_stride, int x_div, bool silu_mul) {
+  if (a.dtype != AWQ_DTYPE_BF16 || a.g % 128 || !repacked_supported(a.K, a.N, a.g, a.dtype) || a.ldx < a.K || a.ldx % 8 ||
+      (((uintptr_t)a.x) & 15) || num_blocks < 1 || num_blocks > 65535 || x_div < 1)
+    return AWQ_ERR_BAD_VARIANT;
+  if (a.K / 128 >= 4096 || a.g / 128 >= 4096) return AWQ_ERR_BAD_VARIANT;
+  SxbLaunch l;
+  l.NG = rp_groups(a.N);
+  if (silu_mul && (a.N % 32 || (l.NG & 1))) return AWQ_ERR_BAD_VARIANT;
+  const int G = l.NG >= 8 ? 8 : l.NG >= 6 ? 6 : l.NG >= 4 ? 4 : (l.NG == 3 && !silu_mul) ? 3 : l.NG >= 2 ? 2 : 1;
+  if (silu_mul && (G & 1)) return AWQ_ERR_BAD_VARIANT;
+  l.nwg = (l.NG + G - 1) / G;
+  l.qw_r = (const u32x4_t*)packed_experts;
+  l.zs_r = (const uint32_t*)packed_experts + (size_t)l.NG * (a.K / 128) * 256;
+  const int gk = a.g / 128;                                // kb / gk as a multiply-shift, exact for kb < 4096 (as the dense launcher)
+  int lg = 0;
+  while ((1 << lg) < gk) ++lg;
+  l.gshift = 12 + lg;
+  l.gmul = (int)(((1ll << l.gshift) + gk - 1) / gk);
+  const SxbMoe moe = {row_map, block_expert, slot_scale, expert_stride, x_div};
+  const bool nt = (size_t)a.K * a.N / 2 >= route::kStreamedMinBytes;      // per expert, as the dense launcher decides per matrix
+  if (silu_mul) {
+    switch (G) {
+      case 2: return sxb_go_moe<2, 1>(a, l, num_blocks, moe, nt);
+      case 4: return sxb_go_moe<4, 1>(a, l, num_blocks, moe, nt);
+      case 6: return sxb_go_moe<6, 1>(a, l, num_blocks, moe, nt);
+      default: return sxb_go_moe<8, 1>(a, l, num_blocks, moe, nt);
+    }
+  }
+  switch (G) {
+    case 1: return sxb_go_moe<1, 0>(a, l, num_blocks, moe, nt);
+    case 2: return sxb_go_moe<2, 0>(a, l, num_blocks, moe, nt);
+    case 3: return sxb_go_moe<3, 0>(a, l, num_blocks, moe, nt);
+    case 4: return sxb_go_moe<4, 0>(a, l, num_blocks, moe, nt);
+    case 6: return sxb_go_moe<6, 0>(a, l, num_blocks, moe, nt);
+    default: return sxb_go_moe<8, 0>(a, l, num_blocks, moe, nt);
   }
 }
 

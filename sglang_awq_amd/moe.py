@@ -24,6 +24,11 @@ column-interleaved tensors so SiLU·mul is the GEMV's epilogue), and a forward i
     then one sum over each token's top_k rows.  Ids outside [0, E) (the reference marks the padded tokens of a graph batch
     with -1, layers/moe/topk.py:705-712) contribute zero.
 
+bf16 experts (`params_dtype = torch.bfloat16`, as the reference takes it, awq.py:669-757) run the same structure on the bf16 kernels:
+16-row blocks on `gemv_sharedx_bf16_kernel`, 128-row blocks on `gemm_repacked_pipelined_bf16_kernel` from 32 rows per expert on
+average; no slot route, no 64-row tiles, and the combine is the tensor form (fp32 sum, one rounding) because `awq_aux_moe_sum` is fp16 only.  Every "fp16" below
+then reads "bf16".
+
 Arithmetic (what the reference's fused MoE computes, fused_moe.py fused_experts_impl): per (token, expert) pair
 act = fp16(silu(fp16 gate)) * fp16 up of the fp16-rounded w13 output, y = fp16(routed weight * fp32 sums of act @ W2),
 output = fp16(sum over the token's pairs) (* routed_scaling_factor if the runner config carries one).  No fixture of the
@@ -39,6 +44,8 @@ import torch
 
 from . import _lib
 from .awq import AWQConfig
+
+_DTYPES = {torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 
 
 def select_experts(router_logits: torch.Tensor, top_k: int, renormalize: bool = True):
@@ -74,6 +81,10 @@ class AWQMoEMethod:
     # against ~340; DeepSeek-V3-like: 1.7 ms either way); from 17 rows it pays a second stream while a 64-row tile does not
     # (profiles/r03_time_moe_tile_route.txt).
     TILE_ROUTE_MIN_ROWS_PER_EXPERT = 16
+    # bf16 has 128-row tiles only, which pad every expert's rows to 128, so they take over later: measured (profiles/time_moe_bf16.txt,
+    # 16-row blocks / 128-row tiles, us) Mixtral-like at 16 / 24 / 32 / 40 rows per expert 345 / 482, 436 / 550, 554 / 552, 613 / 556;
+    # DeepSeek-V3-like at 16 / 20 / 24 / 32 rows per expert 2424 / 3146, 2969 / 3353, 3314 / 3413, 4057 / 3604
+    TILE_ROUTE_MIN_ROWS_PER_EXPERT_BF16 = 32
     # Below this average load the tiles are 64 rows tall (less padding in every expert's last tile, two workgroups per CU), above it 128
     # (Mixtral-like experts at 1024 rows each: 3662 vs 3755 us; at 512 rows a tie; DeepSeek-V3-like at 512 rows: 64-row tiles 10 % faster)
     TILE_ROUTE_WIDE_ROWS_PER_EXPERT = 768
@@ -131,12 +142,13 @@ class AWQMoEMethod:
 
         E, K, I = layer.num_experts, layer.hidden_size, layer.intermediate_size_per_partition
         g = self.quant_config.group_size
-        if not layer.w13_qweight.is_cuda or layer.w13_scales.dtype != torch.float16:
-            raise NotImplementedError("AWQMoEMethod: fp16 experts on a HIP device only")
+        if not layer.w13_qweight.is_cuda or layer.w13_scales.dtype not in _DTYPES or layer.w2_scales.dtype != layer.w13_scales.dtype:
+            raise NotImplementedError("AWQMoEMethod: fp16 or bf16 experts on a HIP device only")
         lib = _lib.load()
-        b13, b2 = lib.awq_repacked_bytes(K, 2 * I, g, _lib.DTYPE_F16), lib.awq_repacked_bytes(I, K, g, _lib.DTYPE_F16)
+        dt = _DTYPES[layer.w13_scales.dtype]
+        b13, b2 = lib.awq_repacked_bytes(K, 2 * I, g, dt), lib.awq_repacked_bytes(I, K, g, dt)
         if b13 == 0 or b2 == 0 or g % 128:
-            raise NotImplementedError(f"AWQMoEMethod: no fragment-major layout for K={K} I={I} group_size={g} (fp16, multiples of 128)")
+            raise NotImplementedError(f"AWQMoEMethod: no fragment-major layout for K={K} I={I} group_size={g} (fp16 / bf16, multiples of 128)")
         dev = layer.w13_qweight.device
         layer.w13_packed = torch.empty((E, b13), dtype=torch.uint8, device=dev)
         layer.w2_packed = torch.empty((E, b2), dtype=torch.uint8, device=dev)
@@ -161,9 +173,12 @@ class AWQMoEMethod:
     def _moe_blocks(self, x, packed, row_map, block_expert, slot_scale, pairs, x_div, K, N, silu, tiles=0):
         g = self.quant_config.group_size
         # rows of padded / dropped pairs are never written by the kernel: the combine launch skips them by expert id (no zero-fill launch);
-        # only the tensor-op fallback of the combine (K % 8 != 0) needs zeros
-        alloc = torch.empty if K % 8 == 0 and N % 8 == 0 else torch.zeros
-        y = alloc((pairs, N // 2 if silu else N), dtype=torch.float16, device=x.device)
+        # only the tensor-op form of the combine (K % 8 != 0; bf16 always, on its w2 stage) needs zeros
+        if x.dtype == torch.float16:
+            alloc = torch.empty if K % 8 == 0 and N % 8 == 0 else torch.zeros
+        else:
+            alloc = torch.empty if silu else torch.zeros
+        y = alloc((pairs, N // 2 if silu else N), dtype=x.dtype, device=x.device)
         # tiles = 64 / 128: rows per block on the MFMA tile kernel; 0: 16-row blocks on the GEMV
         rows_arg = (int(tiles),) if tiles else ()
         fn = _lib.load().awq_aux_moe_gemm_blocks if tiles else _lib.load().awq_aux_moe_gemv_blocks
@@ -171,7 +186,7 @@ class AWQMoEMethod:
                                                  packed.stride(0), ctypes.c_void_p(row_map.data_ptr()),
                                                  ctypes.c_void_p(block_expert.data_ptr()), block_expert.numel(), *rows_arg,
                                                  ctypes.c_void_p(slot_scale.data_ptr()) if slot_scale is not None else None,
-                                                 ctypes.c_void_p(y.data_ptr()), K, N, g, _lib.DTYPE_F16, 1 if silu else 0,
+                                                 ctypes.c_void_p(y.data_ptr()), K, N, g, _DTYPES[x.dtype], 1 if silu else 0,
                                                  ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
         if rc == _lib.ERR_BAD_VARIANT:
             return None
@@ -244,10 +259,13 @@ class AWQMoEMethod:
         return StandardCombineInput(hidden_states=out)
 
     def apply_tensors(self, layer: torch.nn.Module, x: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor) -> torch.Tensor:
-        """x [T, K] fp16, topk_weights [T, top_k] fp32, topk_ids [T, top_k] int (ids outside [0, E) = padded) -> [T, K]."""
+        """x [T, K] fp16 / bf16 (the experts' dtype), topk_weights [T, top_k] fp32, topk_ids [T, top_k] int (ids outside [0, E) = padded)
+        -> [T, K]."""
         E, K, I = layer.num_experts, layer.hidden_size, layer.intermediate_size_per_partition
-        if x.dim() != 2 or x.shape[1] != K or x.dtype != torch.float16:
-            raise RuntimeError(f"AWQMoEMethod.apply: x must be fp16 [tokens, {K}]")
+        dtype = layer.w13_scales.dtype
+        fp16 = dtype == torch.float16
+        if x.dim() != 2 or x.shape[1] != K or x.dtype != dtype:
+            raise RuntimeError(f"AWQMoEMethod.apply: x must be {'fp16' if fp16 else 'bf16'} [tokens, {K}]")
         T, top_k = topk_ids.shape
         if T == 0:
             return x.new_empty((0, K))
@@ -256,13 +274,14 @@ class AWQMoEMethod:
         wts = topk_weights.to(torch.float32).contiguous().view(-1)
         pairs = T * top_k
         y = None
-        if pairs <= self.slot_route_max_pairs(E):
+        if fp16 and pairs <= self.slot_route_max_pairs(E):          # (bf16 has no slot route: 16-row blocks from the first pair)
             act = self._moe_gemv(x, layer.w13_packed, ids, None, pairs, top_k, K, 2 * I, True, E)
             if act is not None:
                 y = self._moe_gemv(act, layer.w2_packed, ids, wts, pairs, 1, I, K, False, E)
-        if y is None and pairs >= self.TILE_ROUTE_MIN_ROWS_PER_EXPERT * E:
+        if y is None and pairs >= (self.TILE_ROUTE_MIN_ROWS_PER_EXPERT if fp16 else self.TILE_ROUTE_MIN_ROWS_PER_EXPERT_BF16) * E:
             # prefill-sized batch: 64- or 128-row blocks on the MFMA tile kernel (each active expert streamed once per tile of its rows)
-            rows = 64 if pairs < self.TILE_ROUTE_WIDE_ROWS_PER_EXPERT * E else 128
+            # (bf16: 128 rows always; the bf16 tile kernel has no 64-row form)
+            rows = 64 if fp16 and pairs < self.TILE_ROUTE_WIDE_ROWS_PER_EXPERT * E else 128
             row_map, block_expert = self.align_blocks_device(ids, E, rows)
             act = self._moe_blocks(x, layer.w13_packed, row_map, block_expert, None, pairs, top_k, K, 2 * I, True, tiles=rows)
             if act is not None:
@@ -275,11 +294,11 @@ class AWQMoEMethod:
             y = self._moe_blocks(act, layer.w2_packed, row_map, block_expert, wts, pairs, 1, I, K, False)
             if y is None:
                 raise NotImplementedError(f"AWQMoEMethod: no kernel for experts K={K} I={I} group_size={self.quant_config.group_size}")
-        if K % 8 == 0:                                        # one launch: fp32 sum over each token's pairs, one rounding
+        if fp16 and K % 8 == 0:                               # one launch: fp32 sum over each token's pairs, one rounding
             out = torch.empty((T, K), dtype=torch.float16, device=x.device)
             rc = _lib.load().awq_aux_moe_sum(ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(out.data_ptr()), T, top_k, K,
                                              ctypes.c_void_p(ids.data_ptr()), E,
                                              ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
             _lib.check(rc, "awq_aux_moe_sum")
             return out
-        return y.view(T, top_k, K).sum(dim=1, dtype=torch.float32).to(torch.float16)
+        return y.view(T, top_k, K).sum(dim=1, dtype=torch.float32).to(dtype)     # (rows of padded / dropped pairs are zeros: _moe_blocks)

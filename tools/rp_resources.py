@@ -2,7 +2,8 @@
 """Print VGPR / scratch use of every gemv_repacked_kernel<G, T, W, NT, MT, EPI> instantiation (hipcc resource remarks).
 
 The launch heuristic's `rp_fits` table in sglang_awq_amd/csrc/awq_repacked.hip is derived from this output;
-run it after touching the kernel.  Exit status 1 if any built instantiation uses scratch.
+run it after touching the kernel.  Exit status 1 if any built instantiation uses scratch.  Also lists the bf16 GEMV and bf16 tile
+kernels by instantiation (dense and AWQ-MoE forms): the MoE launchers choose their strip widths among the rows without scratch.
 """
 import os, re, subprocess, sys, tempfile
 
@@ -38,6 +39,18 @@ def main():
         print("PRO%-2d EPI%d MT%d W%-2d NT%d G%d T%d  vgpr %3d  scratch %4d  occupancy %d" % r)
         bad += r[8] > 0
     print(f"{len(rows)} gemv_repacked_kernel instantiations, {bad} with scratch")
+    # the bf16 kernels by instantiation, dense and AWQ-MoE forms (the MoE launchers choose among the strip widths listed here)
+    for blk in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
+        name = blk.split()[0]
+        m = re.search(r"gemv_sharedx_bf16_kernelILi(\d+)ELi(\d+)ELb(\d)ELi(\d+)ELb(\d)E", name)
+        t = re.search(r"gemm_repacked_pipelined_bf16_kernelILi(\d+)ELb(\d)ELi(\d+)E", name)
+        if not m and not t:
+            continue
+        res = tuple(int(re.search(k + r": (\d+)", blk).group(1)) for k in (" VGPRs", r"AGPRs", r"ScratchSize \[bytes/lane\]", r"LDS Size \[bytes/block\]"))
+        if m:
+            print("sharedx_bf16 G%s MT%s NT%s EPI%s ROWMAP%s  vgpr %3d  agpr %3d  scratch %4d  lds %d" % (m.groups() + res))
+        else:
+            print("tiles_bf16 NJ%s MOE%s EPI%s  vgpr %3d  agpr %3d  scratch %4d  lds %d" % (t.groups() + res))
     # every other kernel of these files (gemv_rp2_kernel, gemv_rpx_kernel, the prefill kernels, repack): scratch must be 0 too
     other, other_bad, worst = 0, [], {}
     for blk in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
