@@ -176,12 +176,24 @@ int awq_gemm_repacked_ws(const void* x, int64_t ldx, const void* packed, const v
  *                    remaining column groups in 192-wide tiles in a second.
  *   AWQ_RP_TILES_BF16_NARROW  the same kernel and domain: 128 x 128 tiles everywhere, one launch.
  *                    The three refuse fp16 and group sizes 32 / 64.
+ *   AWQ_RP_GEMV_BF16  1 <= M <= 16, bf16, group_size % 128 == 0, N <= 32768 (one strip of at most 8 column groups per
+ *                    workgroup), ldx % 8 == 0, x 16-byte aligned, K / 128 < 4096: the straight-line decode GEMV in bf16
+ *                    (awq_repacked_gemv_bf16.hip) — 16 waves, x and the (scale | zero) words staged once per wave through
+ *                    wave-private LDS, a ring of two weight loads per wave, dequantisation kept in fp32 (as
+ *                    AWQ_RP_SHARED_X_BF16) with its per-column constants precomputed into LDS in the one-row form.  ceil(K / 2048) k-blocks per
+ *                    wave: at most 16 units (strip width x k-blocks per wave) with at most 8 k-blocks per wave, at one row up to 32
+ *                    units with at most 16; M x k-blocks per wave <= 32; the staging area within 144 KiB of LDS (16 rows: K <= 4096,
+ *                    at K > 2048 on strips of at most 5 column groups).  Every weight is the bf16 awq_dequantize produces
+ *                    (normal scales of magnitude >= 2^-122).  No workspace is used.  Refuses fp16 and group sizes 32 / 64.
+ *                    Error precedence differs from the other variants here: fp16, M > 16 or group_size % 128 != 0 return
+ *                    AWQ_ERR_BAD_VARIANT before the pointer and shape checks (that part of the domain needs no pointer), so such a call
+ *                    is a refused variant even with NULL arguments.
  * Returns AWQ_ERR_BAD_VARIANT for an unknown variant or a shape / dtype outside the variant's domain; nothing is launched then.
  * (Enumerators are only ever added: an added variant does not move AWQ_HIP_ABI_VERSION.)
  */
 enum awq_repacked_variant {
   AWQ_RP_AUTO = 0, AWQ_RP_SHARED_X = 1, AWQ_RP_SHARED_X_WIDE = 2, AWQ_RP_SHARED_X_BF16 = 3,
-  AWQ_RP_TILES_BF16 = 4, AWQ_RP_TILES_BF16_WIDE = 5, AWQ_RP_TILES_BF16_NARROW = 6
+  AWQ_RP_TILES_BF16 = 4, AWQ_RP_TILES_BF16_WIDE = 5, AWQ_RP_TILES_BF16_NARROW = 6, AWQ_RP_GEMV_BF16 = 7
 };
 
 int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const void* bias, void* y, void* workspace,

@@ -40,6 +40,15 @@ static int gemv_one_launch(const GemmArgs& a, const void* packed, bool splitk_sc
 
 static int repacked_dispatch(const GemmArgs& a, const void* packed) {
   const int64_t M = a.M;
+  // bf16, g % 128 == 0, up to 16 rows: the straight-line bf16 GEMV in the cells where it measured faster than the routes below
+  // (route::gemv_bf16_wins); where it has no instantiation for the shape the routes below stay
+  if (a.dtype == AWQ_DTYPE_BF16 && a.g % 128 == 0 && M <= route::kGemvBf16MaxRows) {
+    static const int env_gb = lab_env("AWQ_GEMV_BF16", -1);       // lab knob: 0 = never (the previous route), 1 = wherever its domain allows
+    if (env_gb < 0 ? route::gemv_bf16_wins(M, a.K, a.N) : env_gb != 0) {
+      const int rs = launch_gemv_repacked_bf16(a, packed);
+      if (rs != AWQ_ERR_BAD_VARIANT) return rs;
+    }
+  }
   // bf16, g % 128 == 0, up to 64 rows: the bf16 shared-activation kernels in the cells where they measured faster than the generic
   // routes below (route::sharedx_bf16_wins)
   if (a.dtype == AWQ_DTYPE_BF16 && a.g % 128 == 0 && M <= route::kSharedXBf16MaxRows) {
@@ -290,7 +299,10 @@ int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const v
                          void* stream) {
   if (variant == AWQ_RP_AUTO) return awq_gemm_repacked_ws(x, ldx, packed, bias, y, workspace, workspace_bytes, M, K, N, group_size, dtype, stream);
   const bool tiles_bf16 = variant == AWQ_RP_TILES_BF16 || variant == AWQ_RP_TILES_BF16_WIDE || variant == AWQ_RP_TILES_BF16_NARROW;
-  if (variant != AWQ_RP_SHARED_X && variant != AWQ_RP_SHARED_X_WIDE && variant != AWQ_RP_SHARED_X_BF16 && !tiles_bf16) return AWQ_ERR_BAD_VARIANT;
+  if (variant != AWQ_RP_SHARED_X && variant != AWQ_RP_SHARED_X_WIDE && variant != AWQ_RP_SHARED_X_BF16 && variant != AWQ_RP_GEMV_BF16 && !tiles_bf16)
+    return AWQ_ERR_BAD_VARIANT;
+  // the dtype / row / group-size part of this variant's domain needs no pointer: a call outside it is a refused variant whatever else it carries
+  if (variant == AWQ_RP_GEMV_BF16 && (dtype != AWQ_DTYPE_BF16 || M > route::kGemvBf16MaxRows || group_size % 128)) return AWQ_ERR_BAD_VARIANT;
   if (!packed) return AWQ_ERR_NULL_POINTER;
   if (K <= 0 || N <= 0 || group_size <= 0 || N % 8 || K % group_size || M < 0 || ldx < K) return AWQ_ERR_BAD_SHAPE;
   if (M == 0) return AWQ_OK;
@@ -303,6 +315,7 @@ int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const v
   a.M = (int)M; a.K = (int)K; a.N = (int)N; a.g = (int)group_size; a.dtype = dtype; a.tune = 0;
   a.stream = (hipStream_t)stream;
   if (variant == AWQ_RP_SHARED_X_BF16) return launch_gemv_repacked_sharedx_bf16(a, packed);
+  if (variant == AWQ_RP_GEMV_BF16) return launch_gemv_repacked_bf16(a, packed);
   if (tiles_bf16) return launch_gemm_repacked_tiles_bf16(a, packed, variant == AWQ_RP_TILES_BF16 ? 0 : variant == AWQ_RP_TILES_BF16_WIDE ? 256 : 128);
   return variant == AWQ_RP_SHARED_X ? launch_gemv_repacked_sharedx(a, packed, false) : launch_gemv_repacked_sharedx_wide(a, packed);
 }

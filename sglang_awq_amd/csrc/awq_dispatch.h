@@ -2,7 +2,7 @@
 // Every threshold the launchers use is a named constant here; the launchers (awq_capi.hip: repacked_dispatch; awq_repacked.hip:
 // launch_gemv_repacked; awq_repacked_splitk.hip: rps_plan; awq_repacked_prefill.hip: launch_gemm_repacked_pipelined) only apply them.
 // fp16, group size a multiple of 128 unless noted; g in {32, 64} takes the generic kernels of awq_repacked_ext.hip at every M, and so does
-// bf16 except in the cells of the two bf16 rows below.
+// bf16 except in the cells of the three bf16 rows below.
 //
 //  rows M        matrix                                   kernel                                        measured (us; source)
 //  ------------  ---------------------------------------  --------------------------------------------  ------------------------------------------------
@@ -25,7 +25,11 @@
 //                                                              owns two column groups of a k-block)             (kbench_sharedx_wide_ab.txt)
 //  bf16 1..64    g % 128 == 0, N <= 32768: 17..32 rows on every   gemv_sharedx_bf16_kernel (the 32-row kernel's   4096 x 22016 at 16 / 32 / 64 rows 20.8 -> 18.7 / 40.8 -> 21.4 / 85.4 -> 41.5;
 //                strip width, 1..16 on 5- and 6-group strips,     structure, dequantisation in fp32; 33..64 rows  4096 x 4096 at 32 rows 13.3 -> 9.5 (kbench_sharedx_bf16_ab.txt)
-//                33..64 on N > 8192 (kSharedXBf16MinRows)         as two launches)
+//                33..64 on N > 8192 (kSharedXBf16MinRows); 1..16   as two launches)
+//                only where the row below is not routed
+//  bf16 1..16    g % 128 == 0, N <= 32768: 1..8 rows on every strip     gemv_bf16_kernel (gemv_rp2_kernel's structure:   4096 x 11008 at 1 row 8.90 -> 7.70 (fp16 6.20); 4096 x 4096 4.95 -> 4.47; 4096 x 22016
+//                width, 9..16 rows on G = 1..5 (gemv_bf16_wins);       x + zs staged per wave, ring of two loads;     at 1 / 8 rows 17.6 -> 12.6 / 18.1 -> 13.3; 8192 x 28672 at 1 row 36.6 -> 27.2
+//                consulted first                                      dequantisation in fp32, constants in LDS)       (kbench_gemv_bf16_ab.txt)
 //  bf16 33..     g % 128 == 0, wherever the bf16 GEMV above is    gemm_repacked_pipelined_bf16_kernel: 128 x 256  4096 x 22016 at 128 / 2048 / 4096 rows 87.5 -> 44.5 / 518 -> 367 / 950 -> 702;
 //                not routed (tiles_bf16_wins)                     + 128 x 192 or 128 x 128 tiles, dequantisation  11008 x 4096 at 64 / 2048 rows 215 -> 105 / 226 -> 172
 //                                                                 by v_fma_mix_f32 from the fp16 magic words      (kbench_tiles_bf16_ab.txt)
@@ -184,6 +188,39 @@ inline bool sharedx_bf16_wins(int64_t M, int64_t K, int64_t N) {
   (void)K;
   if (M < 1 || M > kSharedXBf16MaxRows || G > kOneStripMaxGroups) return false;
   return M >= kSharedXBf16MinRows[(M - 1) / 16][G];
+}
+
+// ---- bf16 straight-line GEMV, 1 .. 16 rows (awq_repacked_gemv_bf16.hip; awq_capi.hip: repacked_dispatch, consulted before sharedx_bf16_wins)
+// Routed per (row bucket 1 / 2 .. 8 / 9 .. 16, strip width G) where both runs of the forced kernel (variant 7) were faster than both runs
+// of the parent route (gemv_rpx_kernel; gemv_sharedx_bf16_kernel on G = 5, 6) and the gain is larger than the spread of identical
+// repeated runs (median 0.1 us, at most 0.6).  profiles/kbench_gemv_bf16_ab.txt, us old -> new at 1 / 8 / 16 rows, g = 128, fp16's route
+// on the same shape in brackets; "-": no instantiation (staging area past the LDS, or more than 32 units / staging chunks), the cell
+// keeps its route.  Every measured cell won; a cell without a measurement is left unrouted (9 .. 16 rows on G = 6, 7, 8):
+//   G = 1  4096 x 4096   4.95 -> 4.47 [4.09] / 5.58 -> 5.27 [5.00] / 6.82 -> 5.84 [6.92];  11008 x 4096  10.05 -> 7.73 [6.34] / - / -;
+//          14336 x 4096 (one row, long form) 11.59 -> 9.41 [7.71]
+//   G = 2  4096 x 8192   7.51 -> 6.04 [5.47] / 7.83 -> 6.92 [6.22] / 8.19 -> 7.91 [8.68];  8192 x 7168  11.76 -> 8.97 [7.72] / 12.06 -> 10.25 [10.64] / -;
+//          28672 x 8192 (one row) - (34.3 [22.9]: 173 KiB of staging)
+//   G = 3  4096 x 11008  8.90 -> 7.70 [6.20] / 9.37 -> 8.19 [7.26] / 10.04 -> 9.31 [8.99];  4096 x 12288  9.29 -> 8.00 [6.53] / 9.76 -> 8.52 [7.53] /
+//          10.27 -> 9.66 [9.17]
+//   G = 4  4096 x 16384  11.73 -> 9.44 [8.10] / 11.90 -> 10.75 [9.01] / 12.80 -> 11.54 [10.71]
+//   G = 5  4096 x 20480  16.36 -> 11.96 [9.70] / 16.86 -> 12.32 [10.86] / 17.53 -> 13.74 [13.77]   (parent: the shared-activation kernel)
+//   G = 6  4096 x 22016  17.61 -> 12.62 [10.72] / 18.14 -> 13.32 [11.48] / - (18.8: the shared-activation kernel stays)
+//   G = 7  4096 x 28672  20.16 -> 15.10 [12.91] / 20.74 -> 15.85 [14.08] / -;  8192 x 28672  36.59 -> 27.15 [22.88] / - / -
+//   G = 8  4096 x 32768  21.52 -> 17.27 [14.04] / 22.11 -> 18.10 [17.32] / -
+// The 2 .. 8-row bucket was measured at 8 rows only and the 9 .. 16-row bucket at 16 only; G = 4 .. 8 rest on one matrix each.
+// A routed cell whose shape has no instantiation (deep K at several rows) falls through to the routes below, as before.
+constexpr int kGemvBf16MaxRows = 16;
+// routed cells per (row bucket 1 / 2 .. 8 / 9 .. 16, strip width G)
+constexpr bool kGemvBf16Routed[3][kOneStripMaxGroups + 1] = {
+    {false, true, true, true, true, true, true, true, true},
+    {false, true, true, true, true, true, true, true, true},
+    {false, true, true, true, true, true, false, false, false}};
+// A pure function of the shape: the same call always takes the same route.
+inline bool gemv_bf16_wins(int64_t M, int64_t K, int64_t N) {
+  const int64_t NG = (N + 15) / 16, G = (NG + 255) / 256;
+  (void)K;
+  if (M < 1 || M > kGemvBf16MaxRows || G > kOneStripMaxGroups) return false;
+  return kGemvBf16Routed[M == 1 ? 0 : M <= 8 ? 1 : 2][G];
 }
 
 // ---- prefill tile model (awq_repacked_prefill.hip), in rounds of the 256 CUs

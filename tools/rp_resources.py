@@ -2,13 +2,13 @@
 """Print VGPR / scratch use of every gemv_repacked_kernel<G, T, W, NT, MT, EPI> instantiation (hipcc resource remarks).
 
 The launch heuristic's `rp_fits` table in sglang_awq_amd/csrc/awq_repacked.hip is derived from this output;
-run it after touching the kernel.  Exit status 1 if any built instantiation uses scratch.  Also lists the bf16 GEMV and bf16 tile
-kernels by instantiation (dense and AWQ-MoE forms): the MoE launchers choose their strip widths among the rows without scratch.
+run it after touching the kernel.  Exit status 1 if any built instantiation uses scratch.  Also lists the bf16 GEMVs (shared-activation and
+straight-line, every (G, T, chunks) of the latter) and the bf16 tile kernels by instantiation (dense and AWQ-MoE forms): the MoE launchers choose their strip widths among the rows without scratch.
 """
 import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = [os.path.join(ROOT, "sglang_awq_amd", "csrc", f) for f in ("awq_repacked.hip", "awq_repacked_fused.hip", "awq_repacked_loop.hip", "awq_repacked_sharedx.hip", "awq_repacked_sharedx_wide.hip", "awq_repacked_sharedx_bf16.hip", "awq_repacked_ext.hip",
+SRCS = [os.path.join(ROOT, "sglang_awq_amd", "csrc", f) for f in ("awq_repacked.hip", "awq_repacked_fused.hip", "awq_repacked_loop.hip", "awq_repacked_sharedx.hip", "awq_repacked_sharedx_wide.hip", "awq_repacked_sharedx_bf16.hip", "awq_repacked_gemv_bf16.hip", "awq_repacked_ext.hip",
                                                                    "awq_repacked_prefill.hip", "awq_repacked_prefill_bf16.hip")]
 
 
@@ -44,10 +44,13 @@ def main():
         name = blk.split()[0]
         m = re.search(r"gemv_sharedx_bf16_kernelILi(\d+)ELi(\d+)ELb(\d)ELi(\d+)ELb(\d)E", name)
         t = re.search(r"gemm_repacked_pipelined_bf16_kernelILi(\d+)ELb(\d)ELi(\d+)E", name)
-        if not m and not t:
+        v = re.search(r"gemv_bf16_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E", name)
+        if not m and not t and not v:
             continue
         res = tuple(int(re.search(k + r": (\d+)", blk).group(1)) for k in (" VGPRs", r"AGPRs", r"ScratchSize \[bytes/lane\]", r"LDS Size \[bytes/block\]"))
-        if m:
+        if v:
+            print("gemv_bf16 G%s T%s CHS%s M1_%s  vgpr %3d  agpr %3d  scratch %4d  lds %d" % (v.groups() + res))
+        elif m:
             print("sharedx_bf16 G%s MT%s NT%s EPI%s ROWMAP%s  vgpr %3d  agpr %3d  scratch %4d  lds %d" % (m.groups() + res))
         else:
             print("tiles_bf16 NJ%s MOE%s EPI%s  vgpr %3d  agpr %3d  scratch %4d  lds %d" % (t.groups() + res))
