@@ -188,12 +188,22 @@ int awq_gemm_repacked_ws(const void* x, int64_t ldx, const void* packed, const v
  *                    Error precedence differs from the other variants here: fp16, M > 16 or group_size % 128 != 0 return
  *                    AWQ_ERR_BAD_VARIANT before the pointer and shape checks (that part of the domain needs no pointer), so such a call
  *                    is a refused variant even with NULL arguments.
+ *   AWQ_RP_TILES_SG  any M >= 1, fp16, group_size 32 or 64, ldx % 8 == 0, x 16-byte aligned, spans inside 32-bit buffer offsets
+ *                    (ldx < 2^22): the hand-pipelined MFMA tiles for the small groups (awq_repacked_prefill_sg.hip), planned as the
+ *                    automatic route runs them: 128 x 256 tiles for whole rounds of the CUs + 128 x 192 tiles for the remaining
+ *                    columns, or 128 x 128 tiles where that is cheaper.  Every k-step of 32 rows dequantises with the (scale | zero)
+ *                    word of its own quantisation group; every weight is the fp16 awq_dequantize produces.  No workspace is used.
+ *   AWQ_RP_TILES_SG_WIDE  the same kernel and domain: floor(ceil(N / 16) / 16) whole 256-wide column tiles in one launch, the
+ *                    remaining column groups in 192-wide tiles in a second.
+ *   AWQ_RP_TILES_SG_NARROW  the same kernel and domain: 128 x 128 tiles everywhere, one launch.
+ *                    The three refuse bf16 and group sizes that are multiples of 128.
  * Returns AWQ_ERR_BAD_VARIANT for an unknown variant or a shape / dtype outside the variant's domain; nothing is launched then.
  * (Enumerators are only ever added: an added variant does not move AWQ_HIP_ABI_VERSION.)
  */
 enum awq_repacked_variant {
   AWQ_RP_AUTO = 0, AWQ_RP_SHARED_X = 1, AWQ_RP_SHARED_X_WIDE = 2, AWQ_RP_SHARED_X_BF16 = 3,
-  AWQ_RP_TILES_BF16 = 4, AWQ_RP_TILES_BF16_WIDE = 5, AWQ_RP_TILES_BF16_NARROW = 6, AWQ_RP_GEMV_BF16 = 7
+  AWQ_RP_TILES_BF16 = 4, AWQ_RP_TILES_BF16_WIDE = 5, AWQ_RP_TILES_BF16_NARROW = 6, AWQ_RP_GEMV_BF16 = 7,
+  AWQ_RP_TILES_SG = 8, AWQ_RP_TILES_SG_WIDE = 9, AWQ_RP_TILES_SG_NARROW = 10
 };
 
 int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const void* bias, void* y, void* workspace,

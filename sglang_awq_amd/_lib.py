@@ -42,6 +42,7 @@ GEMM_AUTO, GEMM_GENERIC, GEMM_SKINNY, GEMM_TILED = 0, 1, 2, 3
 RP_AUTO, RP_SHARED_X, RP_SHARED_X_WIDE, RP_SHARED_X_BF16 = 0, 1, 2, 3   # enum awq_repacked_variant
 RP_TILES_BF16, RP_TILES_BF16_WIDE, RP_TILES_BF16_NARROW = 4, 5, 6
 RP_GEMV_BF16 = 7
+RP_TILES_SG, RP_TILES_SG_WIDE, RP_TILES_SG_NARROW = 8, 9, 10
 
 
 

@@ -92,6 +92,15 @@ static int repacked_dispatch(const GemmArgs& a, const void* packed) {
       if (rs != AWQ_ERR_BAD_VARIANT) return rs;
     }
   }
+  // fp16, g in {32, 64}, 33 rows and up: the hand-pipelined small-group tiles in the cells where they measured faster than the generic
+  // tiles (route::tiles_sg_wins)
+  if (a.dtype == AWQ_DTYPE_F16 && (a.g == 32 || a.g == 64)) {
+    static const int env_ts = lab_env("AWQ_TILES_SG", -1);        // lab knob: 0 = never (the previous route), 1 = wherever its domain allows
+    if (env_ts < 0 ? route::tiles_sg_wins(M, a.K, a.N, a.g) : env_ts != 0) {
+      const int rs = launch_gemm_repacked_tiles_sg(a, packed, 0);
+      if (rs != AWQ_ERR_BAD_VARIANT) return rs;
+    }
+  }
   if (!repacked_fast(a.K, a.N, a.g, a.dtype)) return launch_gemm_repacked_tiled(a, packed);   // bf16 / g in {32, 64}: the generic tiles from 33 rows on
   const bool aligned = a.ldx % 8 == 0 && (((uintptr_t)a.x) & 15) == 0;
   const int64_t wide_tiles = ((M + 127) / 128) * ((a.N + 255) / 256);
@@ -299,7 +308,9 @@ int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const v
                          void* stream) {
   if (variant == AWQ_RP_AUTO) return awq_gemm_repacked_ws(x, ldx, packed, bias, y, workspace, workspace_bytes, M, K, N, group_size, dtype, stream);
   const bool tiles_bf16 = variant == AWQ_RP_TILES_BF16 || variant == AWQ_RP_TILES_BF16_WIDE || variant == AWQ_RP_TILES_BF16_NARROW;
-  if (variant != AWQ_RP_SHARED_X && variant != AWQ_RP_SHARED_X_WIDE && variant != AWQ_RP_SHARED_X_BF16 && variant != AWQ_RP_GEMV_BF16 && !tiles_bf16)
+  const bool tiles_sg = variant == AWQ_RP_TILES_SG || variant == AWQ_RP_TILES_SG_WIDE || variant == AWQ_RP_TILES_SG_NARROW;
+  if (variant != AWQ_RP_SHARED_X && variant != AWQ_RP_SHARED_X_WIDE && variant != AWQ_RP_SHARED_X_BF16 && variant != AWQ_RP_GEMV_BF16 && !tiles_bf16 &&
+      !tiles_sg)
     return AWQ_ERR_BAD_VARIANT;
   // the dtype / row / group-size part of this variant's domain needs no pointer: a call outside it is a refused variant whatever else it carries
   if (variant == AWQ_RP_GEMV_BF16 && (dtype != AWQ_DTYPE_BF16 || M > route::kGemvBf16MaxRows || group_size % 128)) return AWQ_ERR_BAD_VARIANT;
@@ -317,6 +328,7 @@ int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const v
   if (variant == AWQ_RP_SHARED_X_BF16) return launch_gemv_repacked_sharedx_bf16(a, packed);
   if (variant == AWQ_RP_GEMV_BF16) return launch_gemv_repacked_bf16(a, packed);
   if (tiles_bf16) return launch_gemm_repacked_tiles_bf16(a, packed, variant == AWQ_RP_TILES_BF16 ? 0 : variant == AWQ_RP_TILES_BF16_WIDE ? 256 : 128);
+  if (tiles_sg) return launch_gemm_repacked_tiles_sg(a, packed, variant == AWQ_RP_TILES_SG ? 0 : variant == AWQ_RP_TILES_SG_WIDE ? 256 : 128);
   return variant == AWQ_RP_SHARED_X ? launch_gemv_repacked_sharedx(a, packed, false) : launch_gemv_repacked_sharedx_wide(a, packed);
 }
 

@@ -1,8 +1,8 @@
 // One place for the (M, K, N) -> kernel choices on the fragment-major layout and the measured crossover points behind them.
 // Every threshold the launchers use is a named constant here; the launchers (awq_capi.hip: repacked_dispatch; awq_repacked.hip:
 // launch_gemv_repacked; awq_repacked_splitk.hip: rps_plan; awq_repacked_prefill.hip: launch_gemm_repacked_pipelined) only apply them.
-// fp16, group size a multiple of 128 unless noted; g in {32, 64} takes the generic kernels of awq_repacked_ext.hip at every M, and so does
-// bf16 except in the cells of the three bf16 rows below.
+// fp16, group size a multiple of 128 unless noted; g in {32, 64} takes the generic kernels of awq_repacked_ext.hip (fp16 from 33 rows: the
+// "g 32 / 64" row below), and so does bf16 except in the cells of the three bf16 rows below.
 //
 //  rows M        matrix                                   kernel                                        measured (us; source)
 //  ------------  ---------------------------------------  --------------------------------------------  ------------------------------------------------
@@ -33,6 +33,9 @@
 //  bf16 33..     g % 128 == 0, wherever the bf16 GEMV above is    gemm_repacked_pipelined_bf16_kernel: 128 x 256  4096 x 22016 at 128 / 2048 / 4096 rows 87.5 -> 44.5 / 518 -> 367 / 950 -> 702;
 //                not routed (tiles_bf16_wins)                     + 128 x 192 or 128 x 128 tiles, dequantisation  11008 x 4096 at 64 / 2048 rows 215 -> 105 / 226 -> 172
 //                                                                 by v_fma_mix_f32 from the fp16 magic words      (kbench_tiles_bf16_ab.txt)
+//  g 32 / 64     fp16, 33 rows up (tiles_sg_wins)                gemm_repacked_pipelined_sg_kernel: the same      4096 x 22016 at 128 / 2048 / 4096 rows, g = 64: 80.2 -> 41.7 / 448 -> 369 / 825 -> 707;
+//  33..                                                          tiles, every k-step its own (scale | zero) word  11008 x 4096 at 64 / 2048 rows, g = 32: 203 -> 98 / 206 -> 173
+//                                                                 read through op_sel (no splat registers)        (kbench_tiles_sg_ab.txt)
 //  33..160       while passes cost less than the tiles     passes of <= 32 rows of the GEMV                a pass 10.3 / 13.2 / 19.7 / 22.8 us on 4096 x 4096 / x 11008 / x 22016 /
 //                (gemv_passes_max: 2..4 passes)                                                           11008 x 4096; under-filled tiles ~1.12 us per k-block: 37-44 / 91 us
 //                                                                                                         (r03_kbench_middle_rows_ab.txt: 4096 x 22016 at 128 rows 78.6 -> 44)
@@ -256,6 +259,40 @@ constexpr int kTilesBf16MinRows = 33;
 inline bool tiles_bf16_wins(int64_t M, int64_t K, int64_t N) {
   (void)K; (void)N;
   return M >= kTilesBf16MinRows;
+}
+
+// ---- fp16 hand-pipelined tiles for group sizes 32 / 64 (awq_repacked_prefill_sg.hip; awq_capi.hip: repacked_dispatch)
+// Round model of its planned form, as above, from full rounds of 16 x 16 tiles at K = 4096 (profiles/kbench_tiles_sg_ab.txt, two runs
+// each): g = 64: 73.2 us for 256-wide tiles, 61.4 for 192-wide, 48.6 for 128-wide -> 0.84 / 0.66; g = 32: 74.8 / 60.9 / 48.3 ->
+// 0.81 / 0.65.  Both ratios are measured and straddle fp16's 0.84 / 0.65, which are kept (the A/B below ran with them).  The second
+// launch was not measured on its own: the fp16 value.  172 128-wide tiles at 256 rows on 4096 x 11008: 41.3 (g = 64) / 41.7 (g = 32)
+// against 59.3 / 62.8 for the 86 wide ones.
+constexpr double kTilesSgRound192 = 0.84;
+constexpr double kTilesSgRound128 = 0.65;
+constexpr double kTilesSgSecondLaunch = 0.02;
+// Routed from 33 rows.  The forced planned form (variant 8) against the parent route (gemm_rpx_tiled_kernel: the same decomposition
+// compiler-scheduled, 128 x 256 tiles only), us old -> new at 33 / 64 / 65 / 96 / 128 / 160 / 256 / 512 / 2048 / 4096 rows (means of the
+// two runs of a cell; identical runs differ by at most 2.5 %, 0.12 % in the median):
+//   4096 x 4096 g = 64  71.2 -> 38.6 / 71.7 -> 38.7 / 71.8 -> 38.7 / 71.9 -> 38.8 / 72.2 -> 39.0 / 72.3 -> 39.1 / 72.6 -> 39.1 / 73.2 -> 40.2 / 84.2 -> 73.7 / 157.6 -> 139.9
+//   4096 x 4096 g = 32  71.6 -> 39.6 / 72.4 -> 39.7 / 72.4 -> 39.8 / 72.5 -> 39.9 / 72.7 -> 40.0 / 72.5 -> 39.5 / 72.7 -> 39.7 / 73.4 -> 40.3 / 84.3 -> 74.8 / 158.4 -> 141.1
+//   4096 x 12288 g = 64  72.9 -> 39.3 / 78.2 -> 39.4 / 78.3 -> 39.5 / 78.9 -> 39.8 / 79.3 -> 40.1 / 74.6 -> 41.3 / 78.6 -> 42.6 / 81.4 -> 59.7 / 235.3 -> 201.5 / 459.0 -> 391.5
+//   4096 x 12288 g = 32  76.5 -> 39.8 / 78.7 -> 39.9 / 78.7 -> 40.1 / 79.1 -> 40.2 / 79.6 -> 40.6 / 77.0 -> 41.4 / 78.7 -> 42.3 / 81.2 -> 59.7 / 237.5 -> 204.4 / 457.5 -> 398.2
+//   4096 x 22016 g = 64  73.5 -> 40.1 / 79.0 -> 40.6 / 78.9 -> 40.2 / 79.6 -> 41.0 / 80.2 -> 41.7 / 76.0 -> 52.9 / 80.2 -> 55.7 / 155.6 -> 105.9 / 448.1 -> 368.6 / 824.6 -> 706.5
+//   4096 x 22016 g = 32  77.1 -> 40.4 / 79.3 -> 40.9 / 79.2 -> 40.8 / 79.7 -> 41.4 / 80.3 -> 42.4 / 78.5 -> 54.0 / 80.6 -> 56.6 / 157.0 -> 107.9 / 450.0 -> 373.3 / 829.4 -> 710.1
+//   11008 x 4096 g = 64  187.9 -> 95.9 / 201.4 -> 95.9 / 201.5 -> 95.9 / 202.3 -> 95.9 / 202.6 -> 96.1 / 187.9 -> 96.1 / 199.6 -> 96.5 / 199.7 -> 97.4 / 205.3 -> 170.2 / 391.4 -> 331.9
+//   11008 x 4096 g = 32  194.9 -> 97.9 / 202.9 -> 97.8 / 202.9 -> 97.7 / 203.4 -> 97.8 / 203.6 -> 98.1 / 194.3 -> 97.4 / 200.0 -> 97.6 / 200.3 -> 98.3 / 205.8 -> 173.0 / 390.0 -> 334.2
+//   8192 x 28672 g = 64  140.2 -> 75.4 / 150.5 -> 76.5 / 150.5 -> 76.7 / 151.5 -> 79.0 / 151.8 -> 82.5 / 143.5 -> 116.1 / 152.6 -> 125.3 / 296.9 -> 236.8 / 1030.7 -> 871.3 / 2049.5 -> 1729.7
+//   8192 x 28672 g = 32  147.2 -> 76.7 / 151.5 -> 78.0 / 151.6 -> 77.6 / 151.9 -> 79.8 / 152.4 -> 82.7 / 149.2 -> 120.3 / 153.5 -> 126.6 / 298.5 -> 239.1 / 1034.5 -> 880.7 / 2052.6 -> 1758.8
+// In every cell both runs of the new kernel beat both runs of the parent, by at least 10 % (4096 x 4096 at 4096 rows): no measured cell
+// lost, so the rule is rows alone; shapes between and beyond the measured ones (other K, N > 32768) were not measured — their parent is
+// the same generic kernel.  The fp16 g = 128 routes on the same shapes: 71.8 / 136.9 us at 2048 / 4096 rows on 4096 x 4096, 687.7 at 4096
+// rows on 4096 x 22016 (g = 64 / 32: 3 % behind); under-filled launches (one tile per CU or fewer: ~1.2 us per k-block) stay up to
+// 3 x behind g = 128's split-K and GEMV-pass routes, which the small groups lack.
+constexpr int kTilesSgMinRows = 33;
+// A pure function of the shape: the same call always takes the same route.
+inline bool tiles_sg_wins(int64_t M, int64_t K, int64_t N, int64_t g) {
+  (void)K; (void)N; (void)g;
+  return M >= kTilesSgMinRows;
 }
 
 }  // namespace route

@@ -92,6 +92,8 @@ int launch_gemv_repacked_sharedx_bf16(const GemmArgs& a, const void* packed);
 // bf16, g % 128 == 0, any M >= 1: hand-pipelined MFMA tiles (awq_repacked_prefill_bf16.hip); width 0 = planned (256-wide tiles for whole
 // rounds + 192-wide remainder, or 128 x 128 tiles), 256 = whole 256-wide tiles + 192-wide remainder, 128 = 128 x 128 tiles; BAD_VARIANT outside
 int launch_gemm_repacked_tiles_bf16(const GemmArgs& a, const void* packed, int width);
+// fp16, g in {32, 64}, any M >= 1: hand-pipelined MFMA tiles for the small groups (awq_repacked_prefill_sg.hip); width as above; BAD_VARIANT outside
+int launch_gemm_repacked_tiles_sg(const GemmArgs& a, const void* packed, int width);
 // bf16, g % 128 == 0, 1 .. 16 rows on N <= 32768: the straight-line decode GEMV in bf16 (awq_repacked_gemv_bf16.hip); BAD_VARIANT outside,
 // and where (strip width, k-blocks per wave, rows) has no instantiation or its staging area does not fit the LDS
 int launch_gemv_repacked_bf16(const GemmArgs& a, const void* packed);

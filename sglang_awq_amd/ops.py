@@ -376,7 +376,9 @@ def awq_gemm_repacked(input: torch.Tensor, packed: torch.Tensor, K: int, N: int,
     matrices wider than 8192 columns; the fp16 variants refuse bf16 and this one refuses fp16), _lib.RP_TILES_BF16 the hand-pipelined
     bf16 MFMA tiles as the automatic route plans them (any M, group_size % 128 == 0), _lib.RP_TILES_BF16_WIDE the same kernel on whole
     256-wide column tiles + a 192-wide remainder, _lib.RP_TILES_BF16_NARROW on 128 x 128 tiles, _lib.RP_GEMV_BF16 the straight-line
-    bf16 decode GEMV (M <= 16, group_size % 128 == 0, N <= 32768; refuses fp16) (include/awq_hip.h: awq_gemm_repacked_ex); each
+    bf16 decode GEMV (M <= 16, group_size % 128 == 0, N <= 32768; refuses fp16), _lib.RP_TILES_SG / _WIDE / _NARROW the hand-pipelined
+    fp16 MFMA tiles for group sizes 32 and 64 in the same three forms (any M; refuse bf16 and group_size % 128 == 0)
+    (include/awq_hip.h: awq_gemm_repacked_ex); each
     raises AwqHipError where it cannot run."""
     dt = input.dtype
     if input.dim() != 2 or input.shape[1] != K or dt not in (torch.float16, torch.bfloat16):

@@ -291,7 +291,7 @@ static int cmd_stamps(int argc, char** argv) {
 
 // decode GEMV on the repacked (MFMA-fragment-major) layout
 static int cmd_rgemm(int argc, char** argv) {
-  if (argc < 6) { fprintf(stderr, "usage: kbench rgemm M K N g [sets] [iters] [graph] [fuse: 1 norm prologue, 2 silu-mul epilogue, 3 both] [variant: 0 auto, 1 shared-x, 2 shared-x wide, 3 shared-x bf16, 4 bf16 tiles (planned), 5 bf16 tiles 256 + 192 wide, 6 bf16 tiles 128 wide, 7 bf16 straight-line GEMV] [dtype: 0 fp16, 1 bf16]\n"); return 2; }
+  if (argc < 6) { fprintf(stderr, "usage: kbench rgemm M K N g [sets] [iters] [graph] [fuse: 1 norm prologue, 2 silu-mul epilogue, 3 both] [variant: 0 auto, 1 shared-x, 2 shared-x wide, 3 shared-x bf16, 4 bf16 tiles (planned), 5 bf16 tiles 256 + 192 wide, 6 bf16 tiles 128 wide, 7 bf16 straight-line GEMV, 8 small-group tiles (planned; fp16, g 32 / 64), 9 small-group tiles 256 + 192 wide, 10 small-group tiles 128 wide] [dtype: 0 fp16, 1 bf16]\n"); return 2; }
   const int M = atoi(argv[2]), K = atoi(argv[3]), N = atoi(argv[4]), g = atoi(argv[5]);
   const int sets = argc > 6 ? atoi(argv[6]) : 16;
   const int iters = argc > 7 ? atoi(argv[7]) : 400;

@@ -3,13 +3,13 @@
 
 The launch heuristic's `rp_fits` table in sglang_awq_amd/csrc/awq_repacked.hip is derived from this output;
 run it after touching the kernel.  Exit status 1 if any built instantiation uses scratch.  Also lists the bf16 GEMVs (shared-activation and
-straight-line, every (G, T, chunks) of the latter) and the bf16 tile kernels by instantiation (dense and AWQ-MoE forms): the MoE launchers choose their strip widths among the rows without scratch.
+straight-line, every (G, T, chunks) of the latter) the bf16 tile kernels by instantiation (dense and AWQ-MoE forms) and the small-group fp16 tile kernels (NJ, GS): the MoE launchers choose their strip widths among the rows without scratch.
 """
 import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRCS = [os.path.join(ROOT, "sglang_awq_amd", "csrc", f) for f in ("awq_repacked.hip", "awq_repacked_fused.hip", "awq_repacked_loop.hip", "awq_repacked_sharedx.hip", "awq_repacked_sharedx_wide.hip", "awq_repacked_sharedx_bf16.hip", "awq_repacked_gemv_bf16.hip", "awq_repacked_ext.hip",
-                                                                   "awq_repacked_prefill.hip", "awq_repacked_prefill_bf16.hip")]
+                                                                   "awq_repacked_prefill.hip", "awq_repacked_prefill_bf16.hip", "awq_repacked_prefill_sg.hip")]
 
 
 def main():
@@ -45,10 +45,13 @@ def main():
         m = re.search(r"gemv_sharedx_bf16_kernelILi(\d+)ELi(\d+)ELb(\d)ELi(\d+)ELb(\d)E", name)
         t = re.search(r"gemm_repacked_pipelined_bf16_kernelILi(\d+)ELb(\d)ELi(\d+)E", name)
         v = re.search(r"gemv_bf16_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E", name)
-        if not m and not t and not v:
+        g = re.search(r"gemm_repacked_pipelined_sg_kernelILi(\d+)ELi(\d+)E", name)
+        if not m and not t and not v and not g:
             continue
         res = tuple(int(re.search(k + r": (\d+)", blk).group(1)) for k in (" VGPRs", r"AGPRs", r"ScratchSize \[bytes/lane\]", r"LDS Size \[bytes/block\]"))
-        if v:
+        if g:
+            print("tiles_sg NJ%s GS%s  vgpr %3d  agpr %3d  scratch %4d  lds %d" % (g.groups() + res))
+        elif v:
             print("gemv_bf16 G%s T%s CHS%s M1_%s  vgpr %3d  agpr %3d  scratch %4d  lds %d" % (v.groups() + res))
         elif m:
             print("sharedx_bf16 G%s MT%s NT%s EPI%s ROWMAP%s  vgpr %3d  agpr %3d  scratch %4d  lds %d" % (m.groups() + res))
