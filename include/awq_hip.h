@@ -139,7 +139,8 @@ int awq_gemm_repacked(const void* x, int64_t ldx, const void* packed, const void
  *     that case runs wide strips with K split across workgroups (fp32 partials summed in fixed order by the last workgroup to arrive);
  *   33 rows and up where the MFMA tiling leaves most CUs without a tile (narrow or deep matrices, up to a few hundred rows): the tile
  *     kernel runs with K split over workgroups, fp32 partial tiles go to the scratch and a second small launch adds them in slice order,
- *     adds the bias and rounds once (11008 x 4096 at 128 rows: 89 -> 26 us).
+ *     adds the bias and rounds once (11008 x 4096 at 128 rows: 89 -> 26 us).  fp16 from 33 rows; bf16 (group_size % 128 == 0) from 65
+ *     rows — up to 64 rows bf16 uses no scratch and the query returns 0.
  * Both are deterministic; sums agree with the no-workspace routes to fp32 rounding, not bit for bit.  The same holds for the
  * shared-activation GEMV (AWQ_RP_SHARED_X below) against the kernels it replaces at 17 .. 32 rows: same per-element rounding of W, fp32
  * accumulation and one final rounding, another fp32 summation order.  workspace == NULL or too small:
@@ -197,13 +198,24 @@ int awq_gemm_repacked_ws(const void* x, int64_t ldx, const void* packed, const v
  *                    remaining column groups in 192-wide tiles in a second.
  *   AWQ_RP_TILES_SG_NARROW  the same kernel and domain: 128 x 128 tiles everywhere, one launch.
  *                    The three refuse bf16 and group sizes that are multiples of 128.
+ *   AWQ_RP_SPLIT_BF16  any M >= 1, bf16, group_size % 128 == 0, N % 4 == 0, ldx % 8 == 0, x 16-byte aligned, spans inside 32-bit
+ *                    buffer offsets, and a 16-byte aligned workspace behind whose 4096-byte head at least two M x N fp32 slices fit:
+ *                    the bf16 MFMA tiles with K split over S workgroups per tile (awq_repacked_prefill_bf16.hip) and a second launch
+ *                    that adds the fp32 partial tiles in slice order, rounds once and adds the bias.  S = min(256 / tiles, 8,
+ *                    (K / 128) / 4, slices the workspace holds); fewer than two slices (K < 1024, or more than 128 tiles): refused.
+ *                    128 x 128 tiles while there are few of them, 128 x 256 beyond, as the automatic route plans it — but wherever
+ *                    the domain allows, not only where it measured faster.  This is the one forced variant that uses the workspace.
+ *   AWQ_RP_SPLIT_BF16_WIDE  the same kernel and domain on 128 x 256 tiles.
+ *   AWQ_RP_SPLIT_BF16_NARROW  the same kernel and domain on 128 x 128 tiles.
+ *                    The three refuse fp16, group sizes 32 / 64 and a missing, misaligned or too small workspace.
  * Returns AWQ_ERR_BAD_VARIANT for an unknown variant or a shape / dtype outside the variant's domain; nothing is launched then.
  * (Enumerators are only ever added: an added variant does not move AWQ_HIP_ABI_VERSION.)
  */
 enum awq_repacked_variant {
   AWQ_RP_AUTO = 0, AWQ_RP_SHARED_X = 1, AWQ_RP_SHARED_X_WIDE = 2, AWQ_RP_SHARED_X_BF16 = 3,
   AWQ_RP_TILES_BF16 = 4, AWQ_RP_TILES_BF16_WIDE = 5, AWQ_RP_TILES_BF16_NARROW = 6, AWQ_RP_GEMV_BF16 = 7,
-  AWQ_RP_TILES_SG = 8, AWQ_RP_TILES_SG_WIDE = 9, AWQ_RP_TILES_SG_NARROW = 10
+  AWQ_RP_TILES_SG = 8, AWQ_RP_TILES_SG_WIDE = 9, AWQ_RP_TILES_SG_NARROW = 10,
+  AWQ_RP_SPLIT_BF16 = 11, AWQ_RP_SPLIT_BF16_WIDE = 12, AWQ_RP_SPLIT_BF16_NARROW = 13
 };
 
 int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const void* bias, void* y, void* workspace,

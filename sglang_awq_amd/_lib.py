@@ -43,6 +43,7 @@ RP_AUTO, RP_SHARED_X, RP_SHARED_X_WIDE, RP_SHARED_X_BF16 = 0, 1, 2, 3   # enum a
 RP_TILES_BF16, RP_TILES_BF16_WIDE, RP_TILES_BF16_NARROW = 4, 5, 6
 RP_GEMV_BF16 = 7
 RP_TILES_SG, RP_TILES_SG_WIDE, RP_TILES_SG_NARROW = 8, 9, 10
+RP_SPLIT_BF16, RP_SPLIT_BF16_WIDE, RP_SPLIT_BF16_NARROW = 11, 12, 13   # the only forced variants that take the workspace
 
 
 

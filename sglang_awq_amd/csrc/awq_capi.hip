@@ -83,6 +83,15 @@ static int repacked_dispatch(const GemmArgs& a, const void* packed) {
     c.y = (char*)a.y + (size_t)16 * a.N * 2;
     return launch_gemv_repacked(c, packed);
   }
+  // bf16, g % 128 == 0, 65 rows and up with a workspace: the bf16 tiles with K split over workgroups in the cells where they measured
+  // faster than the one-workgroup-per-tile launch below (route::split_tiles_bf16_wins); no or too small a workspace: the routes below
+  if (a.dtype == AWQ_DTYPE_BF16 && a.g % 128 == 0 && a.workspace != nullptr && M >= route::kPfSplitBf16MinRows) {
+    static const int env_skb = lab_env("AWQ_PF_SK_BF16", -1);     // lab knob: 0 = never (the previous route), 1 = wherever its domain allows
+    if (env_skb < 0 ? route::split_tiles_bf16_wins(M, a.K, a.N) : env_skb != 0) {
+      const int rs = launch_gemm_repacked_split_tiles_bf16(a, packed, 0);
+      if (rs != AWQ_ERR_BAD_VARIANT) return rs;
+    }
+  }
   // bf16, g % 128 == 0, 33 rows and up: the hand-pipelined bf16 tiles in the cells where they measured faster than the generic tiles
   // (route::tiles_bf16_wins)
   if (a.dtype == AWQ_DTYPE_BF16 && a.g % 128 == 0) {
@@ -276,8 +285,11 @@ int awq_repack(const int32_t* qweight, const void* scales, const int32_t* qzeros
 }
 
 size_t awq_gemm_repacked_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t group_size, int dtype) {
+  // bf16, g % 128 == 0: the split-K bf16 tiles from 65 rows; up to 64 rows bf16 runs its scratch-free GEMV and tile routes
+  if (dtype == AWQ_DTYPE_BF16 && group_size > 0 && group_size % 128 == 0 && repacked_supported(K, N, group_size, dtype))
+    return pf_split_workspace_bytes(M, K, N, dtype);
   if (!repacked_fast(K, N, group_size, dtype)) return 0;
-  const size_t a = rps_workspace_bytes(M, K, N), b = pf_split_workspace_bytes(M, K, N);      // split-K GEMV (9 .. 32 rows) / split-K tiles (33 rows up)
+  const size_t a = rps_workspace_bytes(M, K, N), b = pf_split_workspace_bytes(M, K, N, dtype);      // split-K GEMV (9 .. 32 rows) / split-K tiles (33 rows up)
   return a > b ? a : b;
 }
 
@@ -309,9 +321,12 @@ int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const v
   if (variant == AWQ_RP_AUTO) return awq_gemm_repacked_ws(x, ldx, packed, bias, y, workspace, workspace_bytes, M, K, N, group_size, dtype, stream);
   const bool tiles_bf16 = variant == AWQ_RP_TILES_BF16 || variant == AWQ_RP_TILES_BF16_WIDE || variant == AWQ_RP_TILES_BF16_NARROW;
   const bool tiles_sg = variant == AWQ_RP_TILES_SG || variant == AWQ_RP_TILES_SG_WIDE || variant == AWQ_RP_TILES_SG_NARROW;
+  const bool split_bf16 = variant == AWQ_RP_SPLIT_BF16 || variant == AWQ_RP_SPLIT_BF16_WIDE || variant == AWQ_RP_SPLIT_BF16_NARROW;
   if (variant != AWQ_RP_SHARED_X && variant != AWQ_RP_SHARED_X_WIDE && variant != AWQ_RP_SHARED_X_BF16 && variant != AWQ_RP_GEMV_BF16 && !tiles_bf16 &&
-      !tiles_sg)
+      !tiles_sg && !split_bf16)
     return AWQ_ERR_BAD_VARIANT;
+  // the split-K bf16 tiles are bf16 kernels fed by a workspace: without either the variant is refused whatever else the call carries
+  if (split_bf16 && (dtype != AWQ_DTYPE_BF16 || !workspace)) return AWQ_ERR_BAD_VARIANT;
   // the dtype / row / group-size part of this variant's domain needs no pointer: a call outside it is a refused variant whatever else it carries
   if (variant == AWQ_RP_GEMV_BF16 && (dtype != AWQ_DTYPE_BF16 || M > route::kGemvBf16MaxRows || group_size % 128)) return AWQ_ERR_BAD_VARIANT;
   if (!packed) return AWQ_ERR_NULL_POINTER;
@@ -322,9 +337,11 @@ int awq_gemm_repacked_ex(const void* x, int64_t ldx, const void* packed, const v
   if (variant == AWQ_RP_SHARED_X && M > route::kGemvMaxRows) return AWQ_ERR_BAD_VARIANT;
   GemmArgs a;
   a.x = x; a.ldx = ldx; a.qweight = nullptr; a.scales = nullptr; a.qzeros = nullptr; a.bias = bias; a.y = y;
-  a.workspace = nullptr; a.workspace_bytes = 0;          // the kernel uses none
+  a.workspace = split_bf16 ? workspace : nullptr;        // the other kernels use none
+  a.workspace_bytes = split_bf16 ? workspace_bytes : 0;
   a.M = (int)M; a.K = (int)K; a.N = (int)N; a.g = (int)group_size; a.dtype = dtype; a.tune = 0;
   a.stream = (hipStream_t)stream;
+  if (split_bf16) return launch_gemm_repacked_split_tiles_bf16(a, packed, variant == AWQ_RP_SPLIT_BF16 ? 0 : variant == AWQ_RP_SPLIT_BF16_WIDE ? 256 : 128);
   if (variant == AWQ_RP_SHARED_X_BF16) return launch_gemv_repacked_sharedx_bf16(a, packed);
   if (variant == AWQ_RP_GEMV_BF16) return launch_gemv_repacked_bf16(a, packed);
   if (tiles_bf16) return launch_gemm_repacked_tiles_bf16(a, packed, variant == AWQ_RP_TILES_BF16 ? 0 : variant == AWQ_RP_TILES_BF16_WIDE ? 256 : 128);

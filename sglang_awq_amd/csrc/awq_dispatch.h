@@ -2,7 +2,7 @@
 // Every threshold the launchers use is a named constant here; the launchers (awq_capi.hip: repacked_dispatch; awq_repacked.hip:
 // launch_gemv_repacked; awq_repacked_splitk.hip: rps_plan; awq_repacked_prefill.hip: launch_gemm_repacked_pipelined) only apply them.
 // fp16, group size a multiple of 128 unless noted; g in {32, 64} takes the generic kernels of awq_repacked_ext.hip (fp16 from 33 rows: the
-// "g 32 / 64" row below), and so does bf16 except in the cells of the three bf16 rows below.
+// "g 32 / 64" row below), and so does bf16 except in the cells of the four bf16 rows below.
 //
 //  rows M        matrix                                   kernel                                        measured (us; source)
 //  ------------  ---------------------------------------  --------------------------------------------  ------------------------------------------------
@@ -33,7 +33,10 @@
 //  bf16 33..     g % 128 == 0, wherever the bf16 GEMV above is    gemm_repacked_pipelined_bf16_kernel: 128 x 256  4096 x 22016 at 128 / 2048 / 4096 rows 87.5 -> 44.5 / 518 -> 367 / 950 -> 702;
 //                not routed (tiles_bf16_wins)                     + 128 x 192 or 128 x 128 tiles, dequantisation  11008 x 4096 at 64 / 2048 rows 215 -> 105 / 226 -> 172
 //                                                                 by v_fma_mix_f32 from the fp16 magic words      (kbench_tiles_bf16_ab.txt)
-//  g 32 / 64     fp16, 33 rows up (tiles_sg_wins)                gemm_repacked_pipelined_sg_kernel: the same      4096 x 22016 at 128 / 2048 / 4096 rows, g = 64: 80.2 -> 41.7 / 448 -> 369 / 825 -> 707;
+//  bf16 65..     g % 128 == 0, workspace given, >= 32 k-blocks,   the same kernel with K split over workgroups    11008 x 4096 at 65 / 128 / 512 rows 104.9 -> 24.7 / 105.6 -> 26.8 / 105.1 -> 60.2;
+//                <= 64 wide tiles, or <= 128 on deep matrices     (SPLIT form) + pf_splitk_reduce_kernel<bf16>;   4096 x 4096 at 128 rows 41.9 -> 20.9; 8192 x 8192 79.6 -> 28.2 at 65 rows
+//                or up to 160 rows (split_tiles_bf16_wins);       consulted before the row above                  (kbench_split_tiles_bf16_ab.txt)
+//  g 32 / 64     fp16, 33 rows up (tiles_sg_wins)              gemm_repacked_pipelined_sg_kernel: the same      4096 x 22016 at 128 / 2048 / 4096 rows, g = 64: 80.2 -> 41.7 / 448 -> 369 / 825 -> 707;
 //  33..                                                          tiles, every k-step its own (scale | zero) word  11008 x 4096 at 64 / 2048 rows, g = 32: 203 -> 98 / 206 -> 173
 //                                                                 read through op_sel (no splat registers)        (kbench_tiles_sg_ab.txt)
 //  33..160       while passes cost less than the tiles     passes of <= 32 rows of the GEMV                a pass 10.3 / 13.2 / 19.7 / 22.8 us on 4096 x 4096 / x 11008 / x 22016 /
@@ -253,12 +256,52 @@ constexpr double kTilesBf16SecondLaunch = 0.02;
 // The parent in every routed cell is gemm_rpx_tiled_kernel, the same decomposition compiler-scheduled, and no measured cell lost, so
 // the rule is rows alone; shapes between and beyond the measured ones (other K, N > 32768) were not measured.  The fp16 routes on the
 // same shapes: 72.1 / 137.0 us at 2048 / 4096 rows on 4096 x 4096, 679.6 at 4096 rows on 4096 x 22016 (bf16: 3 % behind); under-filled
-// launches (one tile per CU or fewer: ~1.3 us per k-block) stay 2 .. 4 x behind fp16's split-K and GEMV-pass routes, which bf16 lacks.
+// launches (one tile per CU or fewer: ~1.3 us per k-block) stay 2 .. 4 x behind fp16's split-K and GEMV-pass routes wherever the bf16
+// split-K form below is not routed: without a workspace, and up to 64 rows.
 constexpr int kTilesBf16MinRows = 33;
 // A pure function of the shape: the same call always takes the same route.
 inline bool tiles_bf16_wins(int64_t M, int64_t K, int64_t N) {
   (void)K; (void)N;
   return M >= kTilesBf16MinRows;
+}
+
+// ---- bf16 split-K tiles, 65 rows up, workspace given (awq_repacked_prefill_bf16.hip: pfb_split_plan; awq_capi.hip: repacked_dispatch,
+// consulted before tiles_bf16_wins).  The slice rule shares kPfSplitMaxSlices / kPfSplitMinBlocks with fp16: S = min(256 / tiles, 8,
+// k-blocks / 4, slices the workspace holds).  The forced planned form (variant 11) against the parent route (variant 4: one workgroup per
+// tile, the whole K loop in it), us old -> new at 65 / 96 / 128 / 160 / 256 / 512 rows, g = 128, every cell measured twice (means; identical
+// runs differ by 0.1 us in the median, at most 1.2 us / 2.0 %), fp16's route with its workspace in brackets, "-": fewer than two slices
+// (more than 128 wide tiles, or the 32 MiB of scratch hold one slice): the variant refuses, the cell keeps its route
+// (profiles/kbench_split_tiles_bf16_ab.txt):
+//   4096 x 4096    41.6 -> 16.9 [16.5] / 41.8 -> 18.8 [18.9] / 41.9 -> 20.9 [20.5] / 42.0 -> 21.9 [21.0] / 42.2 -> 24.7 [23.9] / 42.9 -> 33.1 [39.2]
+//   4096 x 12288   42.8 -> 26.0 [25.3] / 43.1 -> 27.5 [27.2] / 43.4 -> 29.7 [29.5] / 43.7 -> 41.9 [39.5] / 44.4 -> 43.6 [40.9] / 60.6 -> - [58.2]
+//   4096 x 22016   43.6 -> 39.7 [38.9] / 43.9 -> 41.7 [39.8] / 44.8 -> 43.4 [40.2] / 55.0 -> - [51.4] / 56.8 -> - [54.3] / 109.0 -> - [103.7]
+//   11008 x 4096   104.9 -> 24.7 [23.5] / 105.1 -> 25.8 [25.0] / 105.6 -> 26.8 [26.1] / 104.8 -> 34.2 [35.8] / 105.1 -> 38.4 [38.4] / 105.1 -> 60.2 [58.7]
+//   8192 x 8192    79.6 -> 28.2 [28.0] / 79.8 -> 30.2 [29.7] / 80.0 -> 32.8 [31.6] / 79.5 -> 44.2 [43.5] / 79.9 -> 48.2 [47.7] / 85.3 -> 79.5 [78.0]
+//   8192 x 28672   82.0 -> 70.5 [68.0] / 82.6 -> 73.4 [72.0] / 84.1 -> 76.6 [75.1] / 121.2 -> - [112.8] / 124.0 -> - [119.6] / 231.7 -> - [223.9]
+// Routed: every cell in which both runs of the new form beat both runs of the parent by more than that spread — all that ran except
+// 4096 x 12288 at 256 rows (96 wide tiles in two slices: 44.4 / 44.5 -> 43.5 / 43.7, 1.6 %, inside the largest spread; an earlier run
+// of the same cell gave 44.2 / 44.4 -> 44.1 / 44.2): the partial traffic of 2 x 256 x 12288 floats cancels what half a K loop of 32
+// k-blocks saves.  The smallest routed gains: 4096 x 22016 at 128 rows 2.3 % (2.5 % in the earlier run), 4096 x 12288 at 160 rows 3.6 %.
+// As a rule over (wide tiles, depth, rows): at most 64 wide tiles at any measured depth; 65 .. 128 wide tiles on matrices of 64 k-blocks
+// and more (8192 x 28672 up to 128 rows: 112 tiles; 8192 x 8192 at 512 rows: 128), on shallower ones up to 160 rows (4096 x 22016 up to
+// 128 rows: 86 tiles; 4096 x 12288 at 160 rows: 96).  Matrices shallower than 32 k-blocks were not measured and keep their route.
+// Tile width of the plan (variants 12 / 13, one run each, us 256-wide | 128-wide): the width with more workgroups wins; at equal
+// counts (both fill the chip) 128-wide on the 32-k-block matrices (4096 x 4096 at 160 / 256 rows 26.1 | 21.9, 28.1 | 24.6: 64 narrow tiles)
+// and 256-wide, with twice the slices, from 64 k-blocks (11008 x 4096 at 160 / 256 rows 34.1 | 37.9, 37.9 | 39.7; 8192 x 8192 at 65 / 96
+// rows 28.3 | 29.3, 30.4 | 30.8: 64 narrow tiles) — narrow there only up to 32 tiles (11008 x 4096 at 65 rows 30.9 | 24.7).
+constexpr int kPfSplitBf16MinRows = 65;           // up to 64 rows bf16 keeps its scratch-free GEMV and tile routes (the workspace query returns 0)
+constexpr int kPfSplitBf16MinDepth = 32;          // routed on matrices at least this many k-blocks deep (nothing shallower was measured)
+constexpr int kPfSplitBf16FewWideTiles = 64;      // ... when the 128 x 256 tiling gives at most this many tiles,
+constexpr int kPfSplitBf16MaxWideTiles = 128;     // ... or at most this many (two slices; also the bound of the workspace query)
+constexpr int kPfSplitBf16DeepBlocks = 64;        //     on matrices at least this many k-blocks deep,
+constexpr int kPfSplitBf16ShallowMaxRows = 160;   //     on shallower ones up to this many rows
+constexpr int kPfSplitBf16NarrowTilesMax = 64;    // 128 x 128 tiles while there are at most this many of them, 128 x 256 beyond;
+constexpr int kPfSplitBf16NarrowTilesMaxDeep = 32;   // ... on matrices of kPfSplitBf16DeepBlocks k-blocks and more, this many
+// A pure function of the shape: the same call (with a workspace) always takes the same route.
+inline bool split_tiles_bf16_wins(int64_t M, int64_t K, int64_t N) {
+  const int64_t wide_tiles = ((M + 127) / 128) * ((N + 255) / 256), KBT = K / 128;
+  if (M < kPfSplitBf16MinRows || KBT < kPfSplitBf16MinDepth || wide_tiles > kPfSplitBf16MaxWideTiles) return false;
+  return wide_tiles <= kPfSplitBf16FewWideTiles || KBT >= kPfSplitBf16DeepBlocks || M <= kPfSplitBf16ShallowMaxRows;
 }
 
 // ---- fp16 hand-pipelined tiles for group sizes 32 / 64 (awq_repacked_prefill_sg.hip; awq_capi.hip: repacked_dispatch)

@@ -105,7 +105,10 @@ int launch_gemm_repacked_pipelined(const GemmArgs& a, const void* packed);   // 
 // under-filled launches with a workspace: the same tiles with K split over workgroups + a reduce launch; BAD_VARIANT where it does not apply
 int launch_gemm_repacked_split_tiles(const GemmArgs& a, const void* packed);
 bool pf_split_plan(const GemmArgs& a, int* NJ_out, int* S_out, int* kb_per_out);
-size_t pf_split_workspace_bytes(int64_t M, int64_t K, int64_t N);
+size_t pf_split_workspace_bytes(int64_t M, int64_t K, int64_t N, int dtype);   // fp16 from 33 rows, bf16 from 65 (g % 128 == 0: the caller's check)
+// bf16, g % 128 == 0, a.workspace given: the bf16 tiles with K split over workgroups + the reduce launch (awq_repacked_prefill_bf16.hip);
+// width 0 = the planned tile width, 128 / 256 = that width; BAD_VARIANT outside its domain or where fewer than two slices come out
+int launch_gemm_repacked_split_tiles_bf16(const GemmArgs& a, const void* packed, int width);
 // the same kernel over expert-sorted 128-row blocks of (token, expert) pairs (AWQ-MoE prefill; awq_aux_moe_gemm_blocks)
 int launch_gemm_repacked_moe_tiles(const GemmArgs& a, const void* packed_experts, const int* row_map, const int* block_expert, int num_blocks,
                                    int block_rows, const float* slot_scale, long long expert_stride, int x_div, bool silu_mul);

@@ -29,4 +29,18 @@ constexpr int kPfBM = 128;                        // rows per workgroup tile
 constexpr size_t kPfSplitHead = 4096;             // the workspace's counter head (zero between calls: other routes' tickets) is left alone
 constexpr int kPfRsrcFlags = 0x00020000;          // raw buffer descriptor, 32-bit data format (gfx9 family)
 
+// y[m][n] = DT(sum over slices of part[s][m][n]) (+ bias, as store_output<DT> adds it): slice order, one rounding of the sum — the second
+// launch of the split-K tile routes (fp16: awq_repacked_prefill.hip; bf16: awq_repacked_prefill_bf16.hip).  MN % 4 == 0 (N % 4 == 0).
+template <int DT>
+__global__ __launch_bounds__(256) void pf_splitk_reduce_kernel(const float* __restrict__ part, const void* __restrict__ bias, void* __restrict__ y,
+                                                               int S, size_t MN, int N) {
+  for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < MN; i += (size_t)gridDim.x * 1024) {
+    float4_t v = *(const float4_t*)(part + i);
+    for (int s2 = 1; s2 < S; ++s2) v += *(const float4_t*)(part + (size_t)s2 * MN + i);
+    const int n = (int)(i % (size_t)N);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) store_output<DT>(y, i + j, v[j], bias, n + j);
+  }
+}
+
 }  // namespace awq

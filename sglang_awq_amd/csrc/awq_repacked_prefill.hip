@@ -397,18 +397,6 @@ __global__ __launch_bounds__(kPfThreads, 1) void gemm_repacked_pipelined_kernel(
   }
 }
 
-// y[m][n] = fp16(sum over slices of part[s][m][n]) (+ bias): slice order, one rounding — the second launch of the split-K tile route
-__global__ __launch_bounds__(256) void pf_splitk_reduce_kernel(const float* __restrict__ part, const void* __restrict__ bias, void* __restrict__ y,
-                                                               int S, size_t MN, int N) {
-  for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < MN; i += (size_t)gridDim.x * 1024) {
-    float4_t v = *(const float4_t*)(part + i);
-    for (int s2 = 1; s2 < S; ++s2) v += *(const float4_t*)(part + (size_t)s2 * MN + i);
-    const int n = (int)(i % (size_t)N);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) store_output<AWQ_DTYPE_F16>(y, i + j, v[j], bias, n + j);
-  }
-}
-
 template <int NJ, int MI = 8>
 static int pf_launch_region(const GemmArgs& a, const u32x4_t* qw_r, const uint32_t* zs_r, int NG, int cg_base, int ng_region) {
   constexpr int BM = MI * 16;
@@ -468,7 +456,7 @@ static int pf_launch_split(const GemmArgs& a, const u32x4_t* qw_r, const uint32_
                      PfSplit{part, S, kb_per});
   const size_t MN = (size_t)a.M * a.N;
   const unsigned blocks = (unsigned)((MN / 4 + 255) / 256 < 2048 ? (MN / 4 + 255) / 256 : 2048);
-  hipLaunchKernelGGL(pf_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, a.stream, (const float*)part, a.bias, a.y, S, MN, a.N);
+  hipLaunchKernelGGL(pf_splitk_reduce_kernel<AWQ_DTYPE_F16>, dim3(blocks), dim3(256), 0, a.stream, (const float*)part, a.bias, a.y, S, MN, a.N);
   return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
 
@@ -508,10 +496,11 @@ bool pf_split_plan(const GemmArgs& a, int* NJ_out, int* S_out, int* kb_per_out) 
 
 // Scratch the split-K tile route would use for this shape (0: not applicable), at most kPfSplitHead + 32 MiB (the budget of the Python
 // shim's per-stream buffer): the plan with as many slices as fit.
-size_t pf_split_workspace_bytes(int64_t M, int64_t K, int64_t N) {
-  if (M < route::kPfSplitMinRows || N % 4 || K % 128) return 0;
+size_t pf_split_workspace_bytes(int64_t M, int64_t K, int64_t N, int dtype) {
+  const bool bf16 = dtype == AWQ_DTYPE_BF16;              // the bf16 tiles' plan (awq_repacked_prefill_bf16.hip): the same closed form from 65 rows
+  if (M < (bf16 ? route::kPfSplitBf16MinRows : route::kPfSplitMinRows) || N % 4 || K % 128) return 0;
   const int64_t wide_tiles = ((M + 127) / 128) * ((N + 255) / 256);
-  if (wide_tiles > route::kPfSplitMaxWideTiles) return 0;
+  if (wide_tiles > (bf16 ? route::kPfSplitBf16MaxWideTiles : route::kPfSplitMaxWideTiles)) return 0;
   const size_t slice_bytes = (size_t)M * N * sizeof(float), budget = (size_t)32 << 20;
   int S = (int)(256 / wide_tiles) * 2;                      // (the narrow tiling may take twice the slices of the wide one; the plan decides)
   if (S > route::kPfSplitMaxSlices) S = route::kPfSplitMaxSlices;

@@ -42,6 +42,11 @@
 // expert) pairs, the expert chosen per row tile, x rows gathered and output rows scattered through row_map — see PfbMoe below.  Only the
 // tile order, the x offsets and the epilogue differ from the dense form (198 / 199 VGPRs + 128 AGPRs, zero scratch, as the dense 199).
 // 64-row tiles (MI = 4) would need a slot table of their own (17 ops behind 4 MFMAs) and are not built.
+//
+// Split-K form (template parameter SPLIT at NJ = 2 / 4, dense; AWQ_RP_SPLIT_BF16 / _WIDE / _NARROW and, from 65 rows with a workspace,
+// the automatic route): under-filled launches cut K over workgroups, fp32 partial tiles go to the workspace and a second launch adds
+// them — see PfbSplit below and pfb_split_plan.  The loop body is the unsplit one: only where K starts and ends, the tile order and
+// the epilogue differ (198 VGPRs + 128 AGPRs / 141 + 64, zero scratch).
 #include <cstdlib>
 
 #include "awq_prefill_common.h"
@@ -133,14 +138,26 @@ struct PfbMoe {
   int x_div;
 };
 
-template <int NJ, bool MOE = false, int EPI = 0>
+// Split-K over workgroups for under-filled launches (SPLIT; dense form, NJ = 2 / 4; 65 rows up, a workspace given): the launch has
+// tiles x S workgroups, slice s owns the k-blocks [s kb_per, min(K / 128, (s + 1) kb_per)) and everything that walks K starts at its first
+// one; the look-ahead of a slice's last k-block is clamped to the slice as the unsplit kernel clamps it to the matrix.  A workgroup writes
+// its fp32 partial tile to part[slice][M][N] with plain stores; pf_splitk_reduce_kernel<bf16> (a second launch: the kernel boundary orders
+// them) adds the slices in slice order, rounds once and adds the bias.  A template parameter, so the unsplit forms compile as before.
+struct PfbSplit {
+  float* part;
+  int S;
+  int kb_per;
+};
+
+template <int NJ, bool MOE = false, int EPI = 0, bool SPLIT = false>
 __global__ __launch_bounds__(kPfbThreads, 1) void gemm_repacked_pipelined_bf16_kernel(const uint16_t* __restrict__ x, int64_t ldx,
                                                                                        const u32x4_t* __restrict__ qw_r,
                                                                                        const uint32_t* __restrict__ zs_r,
                                                                                        const void* __restrict__ bias, void* __restrict__ y,
                                                                                        int M, int K, int N, int g, int NG, int nbx, int nby,
-                                                                                       int cg_base, int ng_region, PfbMoe moe) {
+                                                                                       int cg_base, int ng_region, PfbMoe moe, PfbSplit split) {
   static_assert(NJ >= 2 && NJ <= 4, "128 x 128 .. 128 x 256 tiles");
+  static_assert(!SPLIT || (!MOE && NJ != 3), "split-K: dense 128 x 128 / 128 x 256 tiles");
   static_assert(!MOE || NJ == 4, "expert blocks run 128 x 256 tiles");
   static_assert(!EPI || MOE, "SiLU-mul epilogue: whole (gate, up) pairs per wave, MoE form only");
   extern __shared__ __attribute__((aligned(16))) unsigned char As[];      // 2 x 32 KiB
@@ -148,20 +165,25 @@ __global__ __launch_bounds__(kPfbThreads, 1) void gemm_repacked_pipelined_bf16_k
   const int tid = threadIdx.x, lane = tid & 63;
   const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);        // wave-uniform: every weight / scale address is an SGPR base + a lane offset
   const int q = lane >> 4, r = lane & 15;
-  const int KB = K / 128, groups = K / g, kpg = g / 128;
+  const int KBT = K / 128, groups = K / g, kpg = g / 128;
 
-  const int nwg = nbx * nby, bid = blockIdx.x;
+  const int ntile = nbx * nby, nwg = SPLIT ? ntile * split.S : ntile, bid = blockIdx.x;
   const int xcd = bid & 7, qd = nwg >> 3, rem = nwg & 7;
-  const int logical = (xcd < rem ? xcd * (qd + 1) : rem * (qd + 1) + (xcd - rem) * qd) + (bid >> 3);
+  const int logical_all = (xcd < rem ? xcd * (qd + 1) : rem * (qd + 1) + (xcd - rem) * qd) + (bid >> 3);
+  const int slice = SPLIT ? logical_all / ntile : 0, logical = SPLIT ? logical_all - slice * ntile : logical_all;
+  const int k0 = SPLIT ? slice * split.kb_per : 0;                  // this workgroup's k-blocks: [k0, k0 + KB)
+  const int KB = SPLIT ? (KBT - k0 < split.kb_per ? KBT - k0 : split.kb_per) : KBT;
   // the 32 tiles an XCD runs together cover 4 row tiles x 8 column tiles: x and weights each shared in its L2 (see the fp16 kernel)
   const int sb_tiles = kPfbRowBlock * nbx, sb = logical / sb_tiles, in_sb = logical - sb * sb_tiles;
   const int rows_sb = nby - sb * kPfbRowBlock < kPfbRowBlock ? nby - sb * kPfbRowBlock : kPfbRowBlock;
   int bm = (sb * kPfbRowBlock + in_sb % rows_sb) * BM;
   int cg_tile = cg_base + (in_sb / rows_sb) * (4 * NJ) + wn * NJ;             // this wave's first column group
   const int cg_end = cg_base + ng_region < NG ? cg_base + ng_region : NG;
-  if constexpr (MOE) {
-    bm = (logical / nbx) * BM;                          // plain order: the column tiles of an expert's row tile together
+  if constexpr (MOE || SPLIT) {                         // plain order: the column tiles of an expert's row tile together / few tiles per slice
+    bm = (logical / nbx) * BM;
     cg_tile = cg_base + (logical % nbx) * (4 * NJ) + wn * NJ;
+  }
+  if constexpr (MOE) {
     const int eid = moe.block_expert[bm / BM];          // uniform over the workgroup, read before any barrier
     if (eid < 0) return;
     qw_r = (const u32x4_t*)((const unsigned char*)qw_r + (long long)eid * moe.expert_stride);
@@ -174,11 +196,11 @@ __global__ __launch_bounds__(kPfbThreads, 1) void gemm_repacked_pipelined_bf16_k
   for (int j = 0; j < NJ; ++j) {
     const int c = cg_tile + j;
     const int cgj = c < cg_end ? c : cg_end - 1;       // clamped: groups outside the region are never stored
-    rw[j] = __builtin_amdgcn_make_buffer_rsrc((void*)(qw_r + (size_t)cgj * KB * 64), 0, KB * 1024, kPfRsrcFlags);
+    rw[j] = __builtin_amdgcn_make_buffer_rsrc((void*)(qw_r + ((size_t)cgj * KBT + k0) * 64), 0, KB * 1024, kPfRsrcFlags);
     zoff_s[j] = (uint32_t)cgj * (uint32_t)groups * 64u;
   }
   const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void*)zs_r, 0, 0x7fffffff, kPfRsrcFlags);
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (MOE ? (size_t)0 : (size_t)bm * ldx)), 0, 0x7fffffff, kPfRsrcFlags);
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (MOE ? (size_t)0 : (size_t)bm * ldx) + (size_t)k0 * 128), 0, 0x7fffffff, kPfRsrcFlags);
   const int lane16 = lane * 16, r4 = r * 4;
 
   u32x4_t a_st[AL];
@@ -221,10 +243,10 @@ __global__ __launch_bounds__(kPfbThreads, 1) void gemm_repacked_pipelined_bf16_k
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[mi][j] = (float4_t){0.f, 0.f, 0.f, 0.f};
 
-  // prologue: x tile 0 into LDS, k-block 0's weights / scales in registers, its first fragment dequantised
+  // prologue: x tile 0 into LDS, k-block 0's weights / scales in registers, its first fragment dequantised (k-blocks counted from k0)
   load_a(0);
-  int grp_n = 0, cnt_n = 0;                            // quantisation group of the next k-block, counted up (no division in the loop)
-  load_b(w_cur, zs_nxt, 0, 0);
+  int grp_n = SPLIT ? k0 / kpg : 0, cnt_n = SPLIT ? k0 - grp_n * kpg : 0;   // quantisation group of the next k-block, counted up (no division in the loop)
+  load_b(w_cur, zs_nxt, 0, grp_n);
 #pragma unroll
   for (int i = 0; i < AL; ++i) store_a1(0, i);
 #pragma unroll
@@ -347,6 +369,30 @@ __global__ __launch_bounds__(kPfbThreads, 1) void gemm_repacked_pipelined_bf16_k
   }
   constexpr int WC = NJ * 16;
   __syncthreads();                                     // every wave has read its last x fragments: the buffers are free
+  if constexpr (SPLIT) {
+    // fp32 partial tile -> part[slice][M][N], no bias, no rounding: wave-private through the idle x buffers 64 rows at a time (64 rows x
+    // WC floats: 16 KiB per wave at NJ = 4, the four waves' the whole 64 KiB), every lane stores 16 bytes of a 256- / 128-byte row run
+    float* const tp = (float*)As + (size_t)wn * (64 * WC);
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) tp[(mi * 16 + 4 * q + i) * WC + j * 16 + r] = acc[half * 4 + mi][j][i];
+      // (a wave's LDS accesses complete in order: no barrier between its own writes and reads)
+#pragma unroll
+      for (int p = 0; p < WC / 4; ++p) {
+        const int f = (p * 64 + lane) * 4;
+        const int row = f / WC, col = f - row * WC;
+        const int m = bm + half * 64 + row, cg = cg_tile + (col >> 4), n = cg * 16 + (col & 15);
+        const float4_t v = *(const float4_t*)(tp + f);
+        if (m < M && cg < cg_end && n < N) *(float4_t*)(split.part + ((size_t)slice * M + m) * N + n) = v;      // (N % 4 == 0: the host's guard)
+      }
+    }
+    return;
+  }
   uint16_t* const tw = (uint16_t*)As + (size_t)wn * (64 * WC);
   const bool n_ok8 = (N % 8) == 0;                     // (16-byte stores need 8-column alignment; otherwise element stores below)
 #pragma unroll
@@ -386,7 +432,7 @@ static int pfb_launch_region(const GemmArgs& a, const u32x4_t* qw_r, const uint3
   static unsigned long long opted[2] = {0ull, 0ull};
   if (!opt_in_dynamic_lds((const void*)gemm_repacked_pipelined_bf16_kernel<NJ>, (int)lds, opted)) return AWQ_ERR_LAUNCH;
   hipLaunchKernelGGL((gemm_repacked_pipelined_bf16_kernel<NJ>), dim3(nbx * nby), dim3(kPfbThreads), lds, a.stream, (const uint16_t*)a.x, a.ldx,
-                     qw_r, zs_r, a.bias, a.y, a.M, a.K, a.N, a.g, NG, nbx, nby, cg_base, ng_region, PfbMoe{nullptr, nullptr, nullptr, 0ll, 1});
+                     qw_r, zs_r, a.bias, a.y, a.M, a.K, a.N, a.g, NG, nbx, nby, cg_base, ng_region, PfbMoe{nullptr, nullptr, nullptr, 0ll, 1}, PfbSplit{nullptr, 1, 0});
   return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
 
@@ -398,7 +444,7 @@ static int pfb_launch_moe(const GemmArgs& a, const u32x4_t* qw_r, const uint32_t
   static unsigned long long opted[2] = {0ull, 0ull};
   if (!opt_in_dynamic_lds((const void*)gemm_repacked_pipelined_bf16_kernel<4, true, EPI>, (int)lds, opted)) return AWQ_ERR_LAUNCH;
   hipLaunchKernelGGL((gemm_repacked_pipelined_bf16_kernel<4, true, EPI>), dim3(nbx * nby), dim3(kPfbThreads), lds, a.stream, (const uint16_t*)a.x,
-                     a.ldx, qw_r, zs_r, nullptr, a.y, num_blocks * kPfBM, a.K, a.N, a.g, NG, nbx, nby, 0, NG, moe);
+                     a.ldx, qw_r, zs_r, nullptr, a.y, num_blocks * kPfBM, a.K, a.N, a.g, NG, nbx, nby, 0, NG, moe, PfbSplit{nullptr, 1, 0});
   return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
 
@@ -455,6 +501,66 @@ int launch_gemm_repacked_tiles_bf16(const GemmArgs& a, const void* packed, int w
   }
   if (gA < NG) return pfb_launch_region<3>(a, qw_r, zs_r, NG, gA, NG - gA);
   return AWQ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ split-K form
+// tiles x S workgroups write fp32 partial tiles into the workspace (behind its 4096-byte counter head, which is left alone), a second
+// launch adds them in slice order, rounds once to bf16 and adds the bias: deterministic, no counters, no in-launch hand-off.
+template <int NJ>
+static int pfb_launch_split(const GemmArgs& a, const u32x4_t* qw_r, const uint32_t* zs_r, int NG, int S, int kb_per) {
+  const int nbx = (NG + 4 * NJ - 1) / (4 * NJ), nby = (a.M + kPfBM - 1) / kPfBM;
+  const size_t lds = 2 * kPfBM * 256;
+  static unsigned long long opted[2] = {0ull, 0ull};
+  if (!opt_in_dynamic_lds((const void*)gemm_repacked_pipelined_bf16_kernel<NJ, false, 0, true>, (int)lds, opted)) return AWQ_ERR_LAUNCH;
+  float* part = (float*)((char*)a.workspace + kPfSplitHead);
+  hipLaunchKernelGGL((gemm_repacked_pipelined_bf16_kernel<NJ, false, 0, true>), dim3(nbx * nby * S), dim3(kPfbThreads), lds, a.stream,
+                     (const uint16_t*)a.x, a.ldx, qw_r, zs_r, nullptr, a.y, a.M, a.K, a.N, a.g, NG, nbx, nby, 0, NG,
+                     PfbMoe{nullptr, nullptr, nullptr, 0ll, 1}, PfbSplit{part, S, kb_per});
+  const size_t MN = (size_t)a.M * a.N;
+  const unsigned blocks = (unsigned)((MN / 4 + 255) / 256 < 2048 ? (MN / 4 + 255) / 256 : 2048);
+  hipLaunchKernelGGL(pf_splitk_reduce_kernel<AWQ_DTYPE_BF16>, dim3(blocks), dim3(256), 0, a.stream, (const float*)part, a.bias, a.y, S, MN, a.N);
+  return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
+}
+
+// The plan: false = outside the domain (fp16, g in {32, 64}, no / misaligned / too small a workspace, N % 4, ldx % 8, spans past the
+// 32-bit buffer offsets) or fewer than two slices.  S = min(256 / tiles: fill the chip once, kPfSplitMaxSlices, slices of at least
+// kPfSplitMinBlocks k-blocks, what the workspace holds), then evened out: ceil(KBT / ceil(KBT / S)) slices, the last one the shortest.
+// width 0: 128 x 128 tiles while there are at most kPfSplitBf16NarrowTilesMax (deep matrices: ...Deep) of them (the other width where that one cannot split);
+// 128 / 256: that width.  Where it pays is not decided here: route::split_tiles_bf16_wins (awq_capi.hip: repacked_dispatch).
+static bool pfb_split_plan(const GemmArgs& a, int width, int* NJ_out, int* S_out, int* kb_per_out) {
+  if (a.dtype != AWQ_DTYPE_BF16 || a.g % 128 || !repacked_supported(a.K, a.N, a.g, a.dtype) || a.M < 1 || a.ldx < a.K || a.ldx % 8 ||
+      (((uintptr_t)a.x) & 15) || !pipelined_addressable(a) || a.N % 4)
+    return false;
+  if (a.norm_h != nullptr || a.moe_slots != 0 || a.silu_mul) return false;
+  if (!a.workspace || (((uintptr_t)a.workspace) & 15) || a.workspace_bytes <= kPfSplitHead) return false;
+  if (width != 0 && width != 128 && width != 256) return false;
+  const int NG = rp_groups(a.N), KBT = a.K / 128, nby = (a.M + kPfBM - 1) / kPfBM;
+  const size_t slice_bytes = (size_t)a.M * a.N * sizeof(float);
+  const size_t s_ws = (a.workspace_bytes - kPfSplitHead) / slice_bytes;
+  const int narrow_max = KBT >= route::kPfSplitBf16DeepBlocks ? route::kPfSplitBf16NarrowTilesMaxDeep : route::kPfSplitBf16NarrowTilesMax;
+  const int first = width == 128 ? 2 : width == 256 ? 4 : (((NG + 7) / 8) * nby <= narrow_max ? 2 : 4);
+  for (int pass = 0; pass < (width ? 1 : 2); ++pass) {
+    const int nj = pass == 0 ? first : 6 - first;
+    const int tiles = ((NG + 4 * nj - 1) / (4 * nj)) * nby;
+    int S = 256 / tiles;
+    if (S > route::kPfSplitMaxSlices) S = route::kPfSplitMaxSlices;
+    if ((size_t)S > s_ws) S = (int)s_ws;
+    if (S > KBT / route::kPfSplitMinBlocks) S = KBT / route::kPfSplitMinBlocks;
+    if (S < 2) continue;
+    const int kb_per = (KBT + S - 1) / S;
+    *NJ_out = nj; *S_out = (KBT + kb_per - 1) / kb_per; *kb_per_out = kb_per;
+    return *S_out >= 2;
+  }
+  return false;
+}
+
+int launch_gemm_repacked_split_tiles_bf16(const GemmArgs& a, const void* packed, int width) {
+  int NJ = 0, S = 0, kb_per = 0;
+  if (!pfb_split_plan(a, width, &NJ, &S, &kb_per)) return AWQ_ERR_BAD_VARIANT;
+  const int NG = rp_groups(a.N);
+  const u32x4_t* qw_r = (const u32x4_t*)packed;
+  const uint32_t* zs_r = (const uint32_t*)packed + (size_t)NG * (a.K / 128) * 256;
+  return NJ == 4 ? pfb_launch_split<4>(a, qw_r, zs_r, NG, S, kb_per) : pfb_launch_split<2>(a, qw_r, zs_r, NG, S, kb_per);
 }
 
 }  // namespace awq

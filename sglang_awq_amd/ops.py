@@ -377,7 +377,9 @@ def awq_gemm_repacked(input: torch.Tensor, packed: torch.Tensor, K: int, N: int,
     bf16 MFMA tiles as the automatic route plans them (any M, group_size % 128 == 0), _lib.RP_TILES_BF16_WIDE the same kernel on whole
     256-wide column tiles + a 192-wide remainder, _lib.RP_TILES_BF16_NARROW on 128 x 128 tiles, _lib.RP_GEMV_BF16 the straight-line
     bf16 decode GEMV (M <= 16, group_size % 128 == 0, N <= 32768; refuses fp16), _lib.RP_TILES_SG / _WIDE / _NARROW the hand-pipelined
-    fp16 MFMA tiles for group sizes 32 and 64 in the same three forms (any M; refuse bf16 and group_size % 128 == 0)
+    fp16 MFMA tiles for group sizes 32 and 64 in the same three forms (any M; refuse bf16 and group_size % 128 == 0),
+    _lib.RP_SPLIT_BF16 / _WIDE / _NARROW the bf16 MFMA tiles with K split over workgroups (bf16, group_size % 128 == 0, K >= 1024;
+    fp32 partial tiles through this stream's scratch buffer and a reduce launch; planned tile width, 128 x 256 or 128 x 128 tiles)
     (include/awq_hip.h: awq_gemm_repacked_ex); each
     raises AwqHipError where it cannot run."""
     dt = input.dtype
@@ -396,8 +398,10 @@ def awq_gemm_repacked(input: torch.Tensor, packed: torch.Tensor, K: int, N: int,
         y = torch.empty((M, N), dtype=dt, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
         if variant != _lib.RP_AUTO:
-            rc = lib.awq_gemm_repacked_ex(_vp(input), ldx, _vp(packed), _vp(bias), _vp(y), None, 0, M, K, N, group_size, _DTYPE_CODE[dt],
-                                          int(variant), ctypes.c_void_p(stream))
+            # the split-K bf16 tiles are the one forced form that takes the per-(device, stream) scratch
+            ws = _workspace(dev, stream) if variant in (_lib.RP_SPLIT_BF16, _lib.RP_SPLIT_BF16_WIDE, _lib.RP_SPLIT_BF16_NARROW) else None
+            rc = lib.awq_gemm_repacked_ex(_vp(input), ldx, _vp(packed), _vp(bias), _vp(y), _vp(ws), ws.numel() if ws is not None else 0,
+                                          M, K, N, group_size, _DTYPE_CODE[dt], int(variant), ctypes.c_void_p(stream))
         elif M > 8 and lib.awq_gemm_repacked_workspace_bytes(M, K, N, group_size, _DTYPE_CODE[dt]):
             # 9 .. 32 rows on a narrow matrix (split-K GEMV) or 33 rows up with few MFMA tiles (split-K tiles): both want the
             # per-(device, stream) scratch (counters + fp32 partials)

@@ -291,7 +291,7 @@ static int cmd_stamps(int argc, char** argv) {
 
 // decode GEMV on the repacked (MFMA-fragment-major) layout
 static int cmd_rgemm(int argc, char** argv) {
-  if (argc < 6) { fprintf(stderr, "usage: kbench rgemm M K N g [sets] [iters] [graph] [fuse: 1 norm prologue, 2 silu-mul epilogue, 3 both] [variant: 0 auto, 1 shared-x, 2 shared-x wide, 3 shared-x bf16, 4 bf16 tiles (planned), 5 bf16 tiles 256 + 192 wide, 6 bf16 tiles 128 wide, 7 bf16 straight-line GEMV, 8 small-group tiles (planned; fp16, g 32 / 64), 9 small-group tiles 256 + 192 wide, 10 small-group tiles 128 wide] [dtype: 0 fp16, 1 bf16]\n"); return 2; }
+  if (argc < 6) { fprintf(stderr, "usage: kbench rgemm M K N g [sets] [iters] [graph] [fuse: 1 norm prologue, 2 silu-mul epilogue, 3 both] [variant: 0 auto, 1 shared-x, 2 shared-x wide, 3 shared-x bf16, 4 bf16 tiles (planned), 5 bf16 tiles 256 + 192 wide, 6 bf16 tiles 128 wide, 7 bf16 straight-line GEMV, 8 small-group tiles (planned; fp16, g 32 / 64), 9 small-group tiles 256 + 192 wide, 10 small-group tiles 128 wide, 11 split-K bf16 tiles (planned width), 12 split-K bf16 tiles 256 wide, 13 split-K bf16 tiles 128 wide] [dtype: 0 fp16, 1 bf16]\n"); return 2; }
   const int M = atoi(argv[2]), K = atoi(argv[3]), N = atoi(argv[4]), g = atoi(argv[5]);
   const int sets = argc > 6 ? atoi(argv[6]) : 16;
   const int iters = argc > 7 ? atoi(argv[7]) : 400;
@@ -325,7 +325,11 @@ static int cmd_rgemm(int argc, char** argv) {
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   // optional scratch (the split-K route for 9..32 rows on narrow matrices): on unless KBENCH_WS=0
   void* ws = nullptr;
-  const size_t ws_bytes = (getenv("KBENCH_WS") && atoi(getenv("KBENCH_WS")) == 0) ? 0 : awq_gemm_repacked_workspace_bytes(M, K, N, g, dtype);
+  // (the forced split-K bf16 tiles, variants 11 .. 13, run wherever their domain allows, also where the query says the automatic route
+  // would not use the scratch: they get the query's upper bound)
+  const bool split_bf16 = variant >= AWQ_RP_SPLIT_BF16 && variant <= AWQ_RP_SPLIT_BF16_NARROW;
+  const size_t ws_bytes = split_bf16 ? (size_t)4096 + ((size_t)32 << 20)
+                          : (getenv("KBENCH_WS") && atoi(getenv("KBENCH_WS")) == 0) ? 0 : awq_gemm_repacked_workspace_bytes(M, K, N, g, dtype);
   if (ws_bytes) { CK(hipMalloc(&ws, ws_bytes)); CK(hipMemset(ws, 0, ws_bytes)); }
   // KBENCH_STREAMS=2 (probe): the launches of a graph alternate between two streams with no dependency between them — how much of the
   // per-launch boundary + ramp disappears when the next kernel may start before the previous one has drained

@@ -43,7 +43,7 @@ def main():
     for blk in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
         name = blk.split()[0]
         m = re.search(r"gemv_sharedx_bf16_kernelILi(\d+)ELi(\d+)ELb(\d)ELi(\d+)ELb(\d)E", name)
-        t = re.search(r"gemm_repacked_pipelined_bf16_kernelILi(\d+)ELb(\d)ELi(\d+)E", name)
+        t = re.search(r"gemm_repacked_pipelined_bf16_kernelILi(\d+)ELb(\d)ELi(\d+)ELb(\d)E", name)
         v = re.search(r"gemv_bf16_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E", name)
         g = re.search(r"gemm_repacked_pipelined_sg_kernelILi(\d+)ELi(\d+)E", name)
         if not m and not t and not v and not g:
@@ -56,7 +56,7 @@ def main():
         elif m:
             print("sharedx_bf16 G%s MT%s NT%s EPI%s ROWMAP%s  vgpr %3d  agpr %3d  scratch %4d  lds %d" % (m.groups() + res))
         else:
-            print("tiles_bf16 NJ%s MOE%s EPI%s  vgpr %3d  agpr %3d  scratch %4d  lds %d" % (t.groups() + res))
+            print("tiles_bf16 NJ%s MOE%s EPI%s SPLIT%s  vgpr %3d  agpr %3d  scratch %4d  lds %d" % (t.groups() + res))
     # every other kernel of these files (gemv_rp2_kernel, gemv_rpx_kernel, the prefill kernels, repack): scratch must be 0 too
     other, other_bad, worst = 0, [], {}
     for blk in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
