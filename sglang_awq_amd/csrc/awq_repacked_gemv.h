@@ -432,11 +432,22 @@ __global__ __launch_bounds__(1024) void gemv_rp2_kernel(const uint16_t* __restri
   for (int i = 0; i < CHT; ++i) *(u32x4_t*)(stg + sdst[i]) = sv[i];
   if (kb0 + T > KB) {
     // ragged last wave (wave-uniform, rare): a k-block past K must contribute nothing.  Its weights were re-read from the last
-    // valid k-block and its x from column 0 (both finite); overwrite its staged (scale | 1024 + zero) words with scale 0, so
-    // every dequantised value is exactly 0.  A second, predicated LDS store behind the first: no select on loaded data.
+    // valid k-block and its x from column 0 of row 0; overwrite its staged (scale | 1024 + zero) words with scale 0, so
+    // every dequantised value is exactly 0, and its staged x with zeros: 0 x NaN or 0 x inf from x[0, 0 .. 127] would otherwise
+    // turn every row NaN.  Second, predicated LDS stores behind the first: no select on loaded data.
     if (lane < NZ) {
       const int c = lane / (T * 4), rem = lane - c * (T * 4), t = rem >> 2, part = rem & 3;
       if (kb0 + t >= KB) *(u32x4_t*)(stg + xbytes + ((c * T + t) * 16 + part * 4) * 4) = (u32x4_t){0x64000000u, 0x64000000u, 0x64000000u, 0x64000000u};
+    }
+#pragma unroll
+    for (int i = 0; i < CHS; ++i) {
+      const int id = lane + 64 * i;
+      if constexpr (M1 && !NORM) {
+        if (id < T * 16 && kb0 * 128 + id * 8 >= K) *(u32x4_t*)(stg + id * 16) = (u32x4_t){0u, 0u, 0u, 0u};
+      } else {
+        const int row = id / (T * 16), cc = id - row * (T * 16);
+        if (id < nx && kb0 * 128 + cc * 8 >= K) *(u32x4_t*)(stg + (row * XS + cc * 8) * 2) = (u32x4_t){0u, 0u, 0u, 0u};
+      }
     }
   }
   __builtin_amdgcn_sched_barrier(0);

@@ -45,7 +45,8 @@
 // nothing to the sum.
 // A k-block past K (ragged last wave, empty waves) re-reads the last valid k-block's weights and x from column 0 (both in bounds) and
 // has its staged constants overwritten — with zeros in the one-row form, the word with (scale 0 | 1024) otherwise — by a second,
-// predicated LDS store behind the first: every dequantised value is exactly 0, and there is no select on loaded data.
+// predicated LDS store behind the first: every dequantised value is exactly 0, and there is no select on loaded data.  Its staged x
+// is overwritten with zeros the same way (0 x NaN and 0 x inf are NaN: a non-finite x[0, 0 .. 127] would reach every row otherwise).
 //
 // LDS.  One row: [16][16 G] floats of partial sums, then per wave the x row, G T x 16 x 16 bytes of constants and a 64-byte dump
 // slot.  2 .. 16 rows: per wave M x rows (T x 128 + 8 halves: rows 16 bytes apart in bank phase), G T x 16 words and a 16-byte dump
@@ -197,7 +198,18 @@ __global__ __launch_bounds__(1024) void gemv_bf16_kernel(const uint16_t* __restr
     }
   }
   if (kb0 + T > KB) {
-    // ragged last wave / empty wave (wave-uniform, rare): a k-block past K must contribute nothing — see the header
+    // ragged last wave / empty wave (wave-uniform, rare): a k-block past K must contribute nothing — see the header.  Its staged x
+    // (re-read from x[0, 0 .. 127]) is overwritten with zeros as well: 0 x NaN or 0 x inf would otherwise turn every row NaN
+#pragma unroll
+    for (int i = 0; i < CHS; ++i) {
+      const int id = lane + 64 * i;
+      if constexpr (M1) {
+        if (id < T * 16 && kb0 * 128 + id * 8 >= K) *(u32x4_t*)(stg + id * 16) = (u32x4_t){0u, 0u, 0u, 0u};
+      } else {
+        const int row = id / (T * 16), cc = id - row * (T * 16);
+        if (id < nx && kb0 * 128 + cc * 8 >= K) *(u32x4_t*)(stg + (row * XS + cc * 8) * 2) = (u32x4_t){0u, 0u, 0u, 0u};
+      }
+    }
 #pragma unroll
     for (int jj = 0; jj < (NZ + 63) / 64; ++jj) {
       const int j = lane + 64 * jj;
